@@ -3,9 +3,14 @@
 histograms (+ % of HBM peak), with RCA PageRank iters/s and EWMA/z
 samples/s alongside (BASELINE.json metric).
 
-One process per GPU.  N=1:  python bench.py
+One process per GPU.  N=1:  python bench.py [--full]
 N>1 (driver):  python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run generates the spans, warms up, times --steps aggregation steps,
+writes the last step's edge table if --dump-outputs DIR is given, and prints
+the headline line.  --full adds the extra legs (--legs) and the CPU baselines
+to that line.
 
 Each rank generates its own shard of synthetic DeathStarBench-SocialNetwork
 spans directly in HBM (generation is outside the
@@ -543,6 +548,19 @@ def load_traffic(n_spans: int) -> tuple[float | None, dict | None]:
     return None, None
 
 
+def dump_outputs(table, out_dir: str) -> None:
+    """The edge table a caller of the timed step receives (with_hist=False:
+    no histogram rows), one <column>.npy per column, as float64: the integer
+    columns stay exact below 2^53, p50/p99 are f64 already.  An edge without
+    spans (count 0) has no quantile: the table's NaN there is written as -1,
+    so that every value in the files is finite.  A few KB in all."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k in ("count", "errors", "sum_us", "min_us", "max_us", "p50_us", "p99_us"):
+        a = np.asarray(getattr(table, k), dtype=np.float64)
+        np.save(d / f"{k}.npy", np.where(np.isnan(a), -1.0, a))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -559,19 +577,32 @@ def main() -> int:
     ap.add_argument("--host-comm", action="store_true",
                     help="N > 1 rehearsal on one device: the ranks merge through libanomod's "
                          "host collective transport over the HostGroup instead of RCCL")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the extra legs (--legs) and the CPU "
+                         "baselines; a plain run sets up, warms up, times the steps and prints "
+                         "the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the edge table of the last timed step to DIR/<column>.npy "
+                         "(float64, -1 for the quantiles of an edge without spans); the inputs "
+                         "are a function of the arguments alone, so two "
+                         "builds can be compared column for column")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline line only")
     ap.add_argument("--legs", default=",".join(LEGS),
-                    help="extra legs to run (comma list of " + ", ".join(LEGS) + ")")
+                    help="with --full: extra legs to run (comma list of " + ", ".join(LEGS) + ")")
     ap.add_argument("--ppr-nodes", type=int, default=100_000)
     ap.add_argument("--ppr-iters", type=int, default=100)
     ap.add_argument("--ewma-series", type=int, default=100_000)
     ap.add_argument("--ewma-steps", type=int, default=131040, help="steps per chunk")
     ap.add_argument("--ewma-chunks", type=int, default=8)
     args = ap.parse_args()
-    legs = set() if args.no_extras else {x for x in args.legs.split(",") if x}
+    legs = {x for x in args.legs.split(",") if x}
     unknown = legs - set(LEGS)
     if unknown:
         ap.error(f"unknown legs {sorted(unknown)}")
+    if args.no_extras or not args.full:
+        legs = set()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -615,7 +646,7 @@ def main() -> int:
         else:  # RCCL; the host transport only if RCCL refuses on every rank (said in the line)
             transport = dist.attach(ctx, dist.RankInfo(rank, world, local), group)
     coll = "RCCL" if transport == "rccl" else "host"
-    cpu_legs = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_legs = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     spec = anomod.SynthSpec("SN", seed=args.seed, p_orphan_ppm=100)
     spans = ctx.generate(spec, args.traces_per_gpu, shard=rank)  # this rank's traces, in HBM
@@ -640,6 +671,8 @@ def main() -> int:
     el = allmax(time.perf_counter() - t0)
     total_spans = allsum(float(spans.n_spans))
     assert int(table.count.sum()) == (int(total_spans) if world > 1 else spans.n_spans)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(table, args.dump_outputs)
 
     k_ms = float(np.mean(kernel_ms))
     bytes_launch = algorithmic_bytes(spans.n_spans, spans.n_traces)

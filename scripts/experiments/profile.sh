@@ -7,10 +7,10 @@ cd "$GRAFT_REPO_ROOT" || exit 9
 export TMPDIR=/tmp
 OUT=gpurun_out/prof
 mkdir -p $OUT
-BENCH_ARGS=${BENCH_ARGS:-"--steps 10 --warmup 2"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --steps 10 --warmup 2"}
 timeout -k 10 300 python3 -u bench.py $BENCH_ARGS > gpurun_out/bench.log 2>&1 || exit $?
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $BENCH_ARGS --no-cpu-baseline > $OUT/bench_trace.log 2>&1 || exit $?
-PMC_ARGS="--steps 2 --warmup 0 --no-cpu-baseline --legs trace_structure,ewma --ewma-chunks 1"
+PMC_ARGS="--full --steps 2 --warmup 0 --no-cpu-baseline --legs trace_structure,ewma --ewma-chunks 1"
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run --output-format csv -- python3 bench.py $PMC_ARGS > $OUT/pmc_fetch.log 2>&1 || exit $?
 timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o run --output-format csv -- python3 bench.py $PMC_ARGS > $OUT/pmc_write.log 2>&1 || exit $?
 if [ "${SQ_PASSES:-1}" = 1 ]; then

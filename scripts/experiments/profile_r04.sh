@@ -9,7 +9,7 @@ cd "$GRAFT_REPO_ROOT" || exit 9
 export TMPDIR=/tmp
 OUT=${1:-$GRAFT_REPO_ROOT/gpurun_out/r04prof}
 mkdir -p "$OUT"
-BENCH_ARGS=${BENCH_ARGS:-"--gpus 1 --steps 20 --warmup 5"}
+BENCH_ARGS=${BENCH_ARGS:-"--full --gpus 1 --steps 20 --warmup 5"}
 if [ "${TRACE:-1}" = 1 ]; then
   timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
     -- python3 -u bench.py $BENCH_ARGS > "$OUT/bench_profiled.log" 2>&1 || exit $?
@@ -18,7 +18,7 @@ if [ "${TRACE:-1}" = 1 ]; then
   rm -rf "$OUT/trace"
 fi
 [ "${PMC:-1}" = 1 ] || { echo done; exit 0; }
-PMC_ARGS=${PMC_ARGS:-"--steps 2 --warmup 1 --no-cpu-baseline --legs trace_structure,ungrouped,tt_width,long_traces,pagerank,ewma --ewma-chunks 1"}
+PMC_ARGS=${PMC_ARGS:-"--full --steps 2 --warmup 1 --no-cpu-baseline --legs trace_structure,ungrouped,tt_width,long_traces,pagerank,ewma --ewma-chunks 1"}
 i=0
 for ctrs in "FETCH_SIZE" "WRITE_SIZE" \
             "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES" \

@@ -170,7 +170,7 @@ def main() -> int:
             "algorithmic_bytes_per_launch": alg, "traffic_over_algorithmic": tot / alg}
     if kernels:
         (out / f"{tag}_pmc.json").write_text(json.dumps(
-            {"round": tag, "correction": CORR, "pmc_bench": "bench.py --steps 2 --warmup 1 "
+            {"round": tag, "correction": CORR, "pmc_bench": "bench.py --full --steps 2 --warmup 1 "
              "--no-cpu-baseline --legs trace_structure,ungrouped,tt_width,long_traces,pagerank,"
              "ewma --ewma-chunks 1 (one process per counter pass)", "kernels": kernels},
             indent=1) + "\n")

@@ -145,7 +145,7 @@ def test_bench_two_ranks_host_comm(tmp_path, mode):
                    WORLD_SIZE="2", LOCAL_RANK=str(r if mode == "host_comm" else 0),
                    ANOMOD_RDZV_DIR=str(tmp_path))
         procs.append(subprocess.Popen(
-            [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3",
+            [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "3",
              "--warmup", "1", "--traces-per-gpu", "30000", "--ppr-nodes", "20000",
              "--ppr-iters", "20", "--ewma-series", "2000", "--ewma-steps", "1920",
              "--ewma-chunks", "2", "--no-cpu-baseline"]
