@@ -18,14 +18,14 @@ from .decode import (MetricMatrix, decode_jaeger, decode_native, load_trace_file
 from .device import (Context, DeviceGraph, DeviceSeries, DeviceSpans, SynthSpec, device_count,
                      device_count_safe, synth_generate_host, synth_graph_csr, synth_services)
 from .engine import (Experiment, Features, default_context, fault_target, features, hit_at,
-                     load_experiment, rank)
+                     load_experiment, rank, trace_window_scores)
 from . import api
 from .segments import SegmentSet, service_name_of, trace_infos
 from .writers import jaeger_to_csv, write_jaeger_csv, write_metric_long_csv
-from .spans import EdgeTable, SpanSet, TraceStructure, edge_rows
+from .spans import EdgeTable, EdgeWindows, SpanSet, TraceStructure, edge_rows
 
 __all__ = [
-    "AnomodError", "Context", "DeviceGraph", "DeviceSeries", "DeviceSpans", "EdgeTable",
+    "AnomodError", "Context", "DeviceGraph", "DeviceSeries", "DeviceSpans", "EdgeTable", "EdgeWindows",
     "EXPORTED_SYMBOLS", "Experiment", "FLAG_ERROR", "Features", "HIST_BINS", "HIST_SUB_BITS",
     "LIB_PATH", "MetricMatrix", "SpanSet", "SynthSpec", "decode_jaeger",
     "decode_metric_long_csv", "decode_metric_long_csv_native", "decode_prometheus_csv_dir",
@@ -35,7 +35,7 @@ __all__ = [
     "rank", "skywalking_parents", "synth_generate_host", "synth_graph_csr", "synth_services", "TraceStructure",
     "SegmentSet", "service_name_of", "trace_infos", "analyze_trace_patterns",
     "jaeger_to_csv", "write_jaeger_csv", "write_metric_long_csv", "decode_native",
-    "load_trace_file", "api",
+    "load_trace_file", "api", "trace_window_scores",
 ]
 
 

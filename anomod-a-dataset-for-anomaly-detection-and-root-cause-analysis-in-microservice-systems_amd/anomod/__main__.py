@@ -25,6 +25,9 @@ def main(argv=None) -> int:
     f.add_argument("--metrics", help="SN metric dir (one CSV per query) or TT long metric CSV")
     f.add_argument("--window", type=int, default=60)
     f.add_argument("--alpha", type=float, default=0.85, help="PageRank damping")
+    f.add_argument("--trace-step", type=float, metavar="SECONDS",
+                   help="also score per-edge time series of the spans' start times, in "
+                        "windows of this many seconds")
     f.add_argument("--out", help="output JSON (default: stdout)")
     j = sub.add_parser("jaeger-to-csv",
                        help="span CSV identical to jaeger_to_csv.py's (collect_trace.sh:70)")
@@ -36,7 +39,7 @@ def main(argv=None) -> int:
         return jaeger_to_csv(args.input, args.output)
 
     exp = load_experiment(args.traces, metrics=args.metrics)
-    feats = features(exp, W=args.window)
+    feats = features(exp, W=args.window, trace_step_s=args.trace_step)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -48,6 +51,9 @@ def main(argv=None) -> int:
         "service_scores": dict(zip(feats.edges.services, map(float, feats.service_scores))),
         "ranking": ranking,
     }
+    if feats.trace_window_scores is not None:
+        doc["trace_window_scores"] = dict(zip(feats.edges.services,
+                                              map(float, feats.trace_window_scores)))
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

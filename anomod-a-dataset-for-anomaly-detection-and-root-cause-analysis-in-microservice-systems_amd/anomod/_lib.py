@@ -28,7 +28,8 @@ OK, EINVAL, EHIP, ERCCL, ENOMEM, ESTATE = 0, -1, -2, -3, -4, -5
 _STATUS = {EINVAL: "EINVAL", EHIP: "EHIP", ERCCL: "ERCCL", ENOMEM: "ENOMEM", ESTATE: "ESTATE"}
 
 (STAGE_EDGE_AGG, STAGE_EDGE_FINAL, STAGE_EDGE_REDUCE, STAGE_EWMA, STAGE_PAGERANK,
- STAGE_TRACE_STRUCT, STAGE_SEGMENTS, STAGE_SUMMARY, STAGE_GROUP) = range(9)
+ STAGE_TRACE_STRUCT, STAGE_SEGMENTS, STAGE_SUMMARY, STAGE_GROUP,
+ STAGE_EDGE_WINDOWS, STAGE_EDGE_WINDOW_KERNEL) = range(11)
 (HOST_GROUP_ALLOC, HOST_GROUP_PINNED, HOST_GROUP_WALL, HOST_UPLOAD_SETUP,
  HOST_SET_ALLOC) = range(5)
 HOST_SLOTS = 5
@@ -68,6 +69,20 @@ class EdgeTableC(C.Structure):
         ("hist", C.POINTER(C.c_uint64)),
         ("p50_us", C.POINTER(C.c_double)),
         ("p99_us", C.POINTER(C.c_double)),
+    ]
+
+
+class EdgeWindowsC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("t0_us", C.c_uint64),
+        ("step_us", C.c_uint64),
+        ("count", C.POINTER(C.c_uint64)),
+        ("errors", C.POINTER(C.c_uint64)),
+        ("sum_us", C.POINTER(C.c_uint64)),
+        ("max_us", C.POINTER(C.c_uint32)),
+        ("outside", C.c_uint64),
     ]
 
 
@@ -157,6 +172,12 @@ _SIGS = {
     "anomod_spans_info": (_i32, [_vp, _P(_u64), _P(_u64)]),
     "anomod_spans_download": (_i32, [_vp, _vp, _P(SpanSoA), _P(_u64)]),
     "anomod_spans_free": (_i32, [_vp]),
+    "anomod_spans_set_start_us": (_i32, [_vp, _vp, _P(_u64)]),
+    "anomod_spans_has_start_us": (_i32, [_vp, _P(_i32)]),
+    "anomod_spans_get_start_us": (_i32, [_vp, _vp, _P(_u64)]),
+    "anomod_spans_fill_start_synthetic": (_i32, [_vp, _vp, _u64, _u64, _u64]),
+    "anomod_edge_windows_spans": (_i32, [_vp, _vp, _P(EdgeWindowsC)]),
+    "anomod_decoded_start_us": (_i32, [_vp, _P(_u64)]),
     "anomod_spans_set_unique_ids": (_i32, [_vp, C.c_int]),
     "anomod_spans_unique_ids": (_i32, [_vp, _P(C.c_int)]),
     "anomod_spans_scan_order": (_i32, [_vp, _P(C.c_int)]),

@@ -65,6 +65,16 @@ def _clamp_u32(v) -> int:
     return 0 if v < 0 else U32_MAX if v > U32_MAX else v
 
 
+def _start_us(v, mult: int = 1) -> int:
+    """A span's start time in epoch microseconds: v * mult when v is a
+    non-negative integer (not a bool, float or string) and the product fits a
+    u64, else 0 — the rule of the native decoders (start_time_us)."""
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+        return 0
+    v *= mult
+    return v if v < (1 << 64) else 0
+
+
 def _truthy_error(v) -> bool:
     return v is True or (isinstance(v, str) and v.lower() == "true")
 
@@ -104,10 +114,13 @@ def decode_jaeger(doc: dict, services: list[str] | None = None) -> SpanSet:
     """Jaeger dump -> SpanSet.  Error flag: tags['error'] true or
     http.status_code >= 500 (tags as kept at jaeger_to_csv.py:55-67)."""
     rows = []
+    starts = []
     trace_ptr = [0]
     trace_ids = []
     for trace in doc.get("data", []) or []:
         rows.extend(jaeger_span_rows({"data": [trace]}))
+        # startTime: integer microseconds (jaeger_to_csv.py:41-43)
+        starts.extend(_start_us(s.get("startTime")) for s in trace.get("spans", []) or [])
         trace_ids.append(trace.get("traceID", ""))
         trace_ptr.append(len(rows))
     names = sorted({r[3] for r in rows}) if services is None else list(services)
@@ -134,7 +147,7 @@ def decode_jaeger(doc: dict, services: list[str] | None = None) -> SpanSet:
         if _truthy_error(tags.get("error")) or _status_ge_500(tags.get("http.status_code")):
             flg[i] = 1
     return SpanSet(names, np.asarray(trace_ptr, np.uint64), th, sid, pid, svc, flg, dur,
-                   trace_ids)
+                   trace_ids, start_us=np.asarray(starts, np.uint64))
 
 
 def merge_jaeger_dumps(dumps: Iterable[dict]) -> dict:
@@ -195,6 +208,7 @@ class _TraceRows:
     services: list
     dur_us: list
     errors: list
+    start_us: list
 
 
 def _dense_ids(nodes: list[str], parents: list) -> tuple[list[int], list[int]]:
@@ -210,7 +224,7 @@ def _build(traces: list[_TraceRows], services: list[str] | None) -> SpanSet:
     names = (sorted({s for t in traces for s in t.services}) if services is None
              else list(services))
     index = {s: i for i, s in enumerate(names)}
-    th, sid, pid, svc, flg, dur, ptr, ids = [], [], [], [], [], [], [0], []
+    th, sid, pid, svc, flg, dur, ptr, ids, start = [], [], [], [], [], [], [0], [], []
     for t in traces:
         s_ids, p_ids = _dense_ids(t.nodes, t.parents)
         h = hash64(str(t.trace_id))
@@ -220,12 +234,13 @@ def _build(traces: list[_TraceRows], services: list[str] | None) -> SpanSet:
         svc.extend(index[s] for s in t.services)
         flg.extend(1 if e else 0 for e in t.errors)
         dur.extend(t.dur_us)
+        start.extend(t.start_us)
         ptr.append(len(sid))
         ids.append(t.trace_id)
     return SpanSet(names, np.asarray(ptr, np.uint64), np.asarray(th, np.uint64),
                    np.asarray(sid, np.uint64), np.asarray(pid, np.uint64),
                    np.asarray(svc, np.uint16), np.asarray(flg, np.uint16),
-                   np.asarray(dur, np.uint32), ids)
+                   np.asarray(dur, np.uint32), ids, start_us=np.asarray(start, np.uint64))
 
 
 def _ms_to_us(start, end) -> int:
@@ -250,7 +265,8 @@ def decode_skywalking_raw(traces: Iterable[list[dict]], services: list[str] | No
             str(kept[0].get("traceId") or ""), nodes, parents,
             [s.get("serviceCode") or "" for s in kept],
             [_ms_to_us(s.get("startTime", 0), s.get("endTime", 0)) for s in kept],
-            [bool(s.get("isError", False)) for s in kept]))
+            [bool(s.get("isError", False)) for s in kept],
+            [_start_us(s.get("startTime"), 1000) for s in kept]))
     return _build(rows, services)
 
 
@@ -269,7 +285,8 @@ def decode_skywalking_payload(payload: dict, services: list[str] | None = None) 
             [s.get("service_code") or "" for s in spans],
             [_ms_to_us(s.get("start_timestamp_ms", 0), s.get("end_timestamp_ms", 0))
              for s in spans],
-            [bool(s.get("is_error", False)) for s in spans]))
+            [bool(s.get("is_error", False)) for s in spans],
+            [_start_us(s.get("start_timestamp_ms"), 1000) for s in spans]))
     return _build(rows, services)
 
 
@@ -511,10 +528,12 @@ def decode_native(data: "bytes | MappedFile", kind: str, services: list[str] | N
         svcs = [lib.anomod_decoded_service(h, i).decode() for i in range(nsv.value)]
         uniq = C.c_int()
         L.check(lib.anomod_decoded_unique_ids(h, C.byref(uniq)))
+        start = np.empty(n, np.uint64)
+        L.check(lib.anomod_decoded_start_us(h, L.ptr(start, C.c_uint64)))
     finally:
         lib.anomod_decoded_free(h)
     # the decoder checked every trace's ids exactly while decoding
-    return SpanSet(svcs, ptr, **arr, unique_ids=bool(uniq.value))
+    return SpanSet(svcs, ptr, **arr, unique_ids=bool(uniq.value), start_us=start)
 
 
 def _first_key(data: bytes) -> str | None:

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import EdgeTable, SpanSet, TraceStructure, edge_rows
+from .spans import EdgeTable, EdgeWindows, SpanSet, TraceStructure, edge_rows
 
 
 @dataclass
@@ -132,6 +132,34 @@ class DeviceSpans:
     def set_hints(self, scan_order: int, hist_form: int):
         L.check(L.lib().anomod_spans_set_hints(self.handle, scan_order, hist_form))
 
+    @property
+    def has_start_us(self) -> bool:
+        h = C.c_int()
+        L.check(L.lib().anomod_spans_has_start_us(self.handle, C.byref(h)))
+        return bool(h.value)
+
+    def set_start_us(self, start_us):
+        """Give the set its start-time column (u64 epoch microseconds, by span
+        position)."""
+        s = np.ascontiguousarray(start_us, np.uint64)
+        if s.shape != (self.n_spans,):
+            raise ValueError(f"start_us has shape {s.shape}, expected ({self.n_spans},)")
+        L.check(L.lib().anomod_spans_set_start_us(self.ctx.handle, self.handle,
+                                                  L.ptr(s, C.c_uint64)), self.ctx.handle)
+
+    def start_us(self) -> np.ndarray:
+        """The start-time column (AnomodError ESTATE when the set has none)."""
+        out = np.empty(self.n_spans, np.uint64)
+        L.check(L.lib().anomod_spans_get_start_us(self.ctx.handle, self.handle,
+                                                  L.ptr(out, C.c_uint64)), self.ctx.handle)
+        return out
+
+    def fill_start_synthetic(self, t0_us: int, period_us: int, gap_us: int = 0):
+        """Start times generated on the device: t0_us + (trace * period_us) //
+        n_traces + position_in_trace * gap_us (grouped sets)."""
+        L.check(L.lib().anomod_spans_fill_start_synthetic(self.ctx.handle, self.handle, t0_us,
+                                                          period_us, gap_us), self.ctx.handle)
+
     def download(self) -> SpanSet:
         n = self.n_spans
         arr = dict(trace_hash=np.empty(n, np.uint64), span_id=np.empty(n, np.uint64),
@@ -143,7 +171,7 @@ class DeviceSpans:
                 self.ctx.handle)
         order, form = self.hints
         return SpanSet(self.services, ptr, **arr, unique_ids=self.unique_ids, scan_order=order,
-                       hist_form=form)
+                       hist_form=form, start_us=self.start_us() if self.has_start_us else None)
 
     def free(self):
         if self.handle:
@@ -289,6 +317,8 @@ class Context:
         d = DeviceSpans(self, h, spans.services)
         d.unique_ids = spans.unique_ids
         d.set_hints(spans.scan_order, spans.hist_form)
+        if spans.start_us is not None:
+            d.set_start_us(spans.start_us)
         return d
 
     def upload_ungrouped(self, spans: SpanSet) -> DeviceSpans:
@@ -374,6 +404,38 @@ class Context:
         if table.hist is not None:
             table.hist = table.hist.reshape(edge_rows(len(spans.services)), L.HIST_BINS)
         return table
+
+    def edge_windows(self, spans: DeviceSpans | SpanSet, t0_us: int, step_us: int,
+                     n_windows: int, outputs=("count", "errors", "sum_us", "max_us")
+                     ) -> EdgeWindows:
+        """Per-window edge table of a grouped set with start times
+        (anomod_edge_windows_spans): window w = (start_us - t0_us) // step_us;
+        spans outside [0, n_windows) are counted in .outside.  Rank-local.
+        `outputs` names the tables to compute (the others stay zero)."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            if spans.start_us is None:
+                raise ValueError("span set has no start_us column")
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            if not 1 <= int(n_windows) <= 65536 or int(n_windows) * edge_rows(S) > 1 << 24:
+                raise L.AnomodError(L.EINVAL, f"n_windows={n_windows} outside [1, 65536] or "
+                                    f"n_windows * edge rows > 2^24 (n_services={S})")
+            win = EdgeWindows.empty(spans.services, t0_us, step_us, n_windows)
+            cs = L.EdgeWindowsC(
+                S, n_windows, t0_us, step_us,
+                L.ptr(win.count if "count" in outputs else None, C.c_uint64),
+                L.ptr(win.errors if "errors" in outputs else None, C.c_uint64),
+                L.ptr(win.sum_us if "sum_us" in outputs else None, C.c_uint64),
+                L.ptr(win.max_us if "max_us" in outputs else None, C.c_uint32), 0)
+            self._check(self._lib.anomod_edge_windows_spans(self.handle, spans.handle,
+                                                            C.byref(cs)))
+            win.outside = int(cs.outside)
+            return win
+        finally:
+            if tmp is not None:
+                tmp.free()
 
     def edge_quantiles_exact(self, spans: DeviceSpans | SpanSet, q_pct=(50, 99)):
         """Exact per-edge order statistics x[(c*q)//100] of the sorted edge

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import EdgeTable, SpanSet
+from .spans import EdgeTable, EdgeWindows, SpanSet, edge_rows
 
 # --------------------------------------------------------------------------
 # Ground-truth labels (experiment name -> faulty service), SURVEY.md §2:
@@ -161,6 +161,10 @@ class Features:
     series: list | None
     service_scores: np.ndarray             # [n_services] anomaly score
     params: dict = field(default_factory=dict)
+    # features(trace_step_s=...): the per-window edge table and the per-service
+    # trace anomaly scores taken from it
+    edge_windows: EdgeWindows | None = None
+    trace_window_scores: np.ndarray | None = None
 
 
 _default_ctx: Context | None = None
@@ -221,10 +225,54 @@ def _latency_shift(cur: EdgeTable, base: EdgeTable, min_count: int = 10) -> np.n
     return ratio.reshape(S + 2, S).max(axis=0)
 
 
+def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int) -> np.ndarray:
+    """Per-service trace anomaly score from the window scores Z [n, 2 * active
+    edges] of win.matrix(): the first score window is dropped (the EWMA
+    variance starts at 0 there), a column scores the mean of its top k =
+    max(1, n_left // 20) windows, and a service takes the max over the columns
+    of the edges it is the child of (row % S; ROOT and ORPHAN rows included)."""
+    out = np.zeros(S)
+    Z = np.asarray(Z, np.float64)[1:]
+    if Z.shape[0] == 0 or Z.shape[1] == 0:
+        return out
+    k = max(1, Z.shape[0] // 20)
+    top = np.sort(Z, axis=0)[-k:].mean(axis=0)
+    active = np.nonzero(win.count.sum(axis=0))[0]
+    child = np.repeat(active % S, 2)
+    np.maximum.at(out, child, top[: child.shape[0]])
+    return out
+
+
+MAX_TRACE_WINDOWS = 65536          # anomod_edge_windows: T <= 65536, T * E <= 2^24
+MAX_TRACE_CELLS = 1 << 24
+
+
+def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float,
+                   min_count: int) -> tuple[EdgeWindows, np.ndarray]:
+    if spans.start_us is None:
+        raise ValueError("features(trace_step_s=...): the span set has no start_us column")
+    step_us = max(1, int(round(step_s * 1e6)))
+    S = spans.n_services
+    nz = spans.start_us[spans.start_us != 0]
+    t0 = int(nz.min()) // step_us * step_us if nz.size else 0
+    T = (int(nz.max()) - t0) // step_us + 1 if nz.size else 1
+    T = max(1, min(T, MAX_TRACE_WINDOWS, MAX_TRACE_CELLS // max(1, edge_rows(S))))
+    win = ctx.edge_windows(spans, t0, step_us, T)
+    mm = win.matrix(min_count).pad_to_multiple(W)
+    if mm.S == 0 or mm.T == 0:
+        return win, np.zeros(S)
+    Z = ctx.ewma_z(mm.X, 2.0 / (W + 1), W, eps)
+    return win, trace_window_scores(Z, win, S)
+
+
 def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              alpha: float | None = None, eps: float = 1e-12, with_hist: bool = True,
-             baseline: "Features | None" = None) -> Features:
-    """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7)."""
+             baseline: "Features | None" = None, trace_step_s: float | None = None,
+             trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5) -> Features:
+    """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
+    trace_step_s (seconds; the span set needs start_us) the spans also go
+    through the per-window edge table -> EWMA/z -> trace_window_scores, and
+    the score gains 0.25 * ts / (1 + ts)."""
     ctx = ctx or default_context()
     edges = ctx.edge_aggregate(exp.spans, with_hist=with_hist)
     S = edges.n_services
@@ -262,9 +310,17 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         lat = _latency_shift(edges, baseline.edges)
     ms = metric_score / (1.0 + metric_score)  # squash z into [0, 1)
     score = err_rate + lat + 0.25 * ms
-    return Features(exp.name, edges, Z, series, score,
-                    {"W": W, "alpha": alpha, "eps": eps,
-                     "components": {"error_rate": err_rate, "latency": lat, "metric": ms}})
+    params = {"W": W, "alpha": alpha, "eps": eps,
+              "components": {"error_rate": err_rate, "latency": lat, "metric": ms}}
+    if trace_step_s is None:
+        return Features(exp.name, edges, Z, series, score, params)
+    win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count)
+    tsq = ts / (1.0 + ts)  # the metric term's squashing
+    params["components"]["trace"] = tsq
+    params.update(trace_step_s=trace_step_s, trace_W=trace_W, trace_eps=trace_eps,
+                  trace_min_count=trace_min_count)
+    return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
+                    edge_windows=win, trace_window_scores=ts)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

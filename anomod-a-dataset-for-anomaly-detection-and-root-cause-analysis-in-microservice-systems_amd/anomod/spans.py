@@ -39,6 +39,9 @@ class SpanSet:
     scan_order: int = field(default=-1, compare=False)
     hist_form: int = field(default=-1, compare=False)
     _keep: list = field(default_factory=list, repr=False, compare=False)
+    # span start times, epoch microseconds (0 = none recorded), or None: the
+    # time axis of Context.edge_windows
+    start_us: np.ndarray | None = field(default=None, compare=False)
 
     def __post_init__(self):
         self.trace_ptr = np.ascontiguousarray(self.trace_ptr, dtype=np.uint64)
@@ -55,6 +58,11 @@ class SpanSet:
                                  f"expected {n}")
         if self.trace_ptr.shape[0] < 1:
             raise ValueError("trace_ptr needs at least one entry")
+        if self.start_us is not None:
+            self.start_us = np.ascontiguousarray(self.start_us, dtype=np.uint64)
+            if self.start_us.shape != (n,):
+                raise ValueError(f"SpanSet column start_us has shape {self.start_us.shape}, "
+                                 f"expected ({n},)")
 
     @property
     def n_spans(self) -> int:
@@ -104,7 +112,8 @@ class SpanSet:
         return SpanSet(list(self.services), new_ptr, self.trace_hash[span_mask],
                        self.span_id[span_mask], self.parent_span_id[span_mask],
                        self.svc[span_mask], self.flags[span_mask], self.dur_us[span_mask], ids,
-                       self.unique_ids)
+                       self.unique_ids,
+                       start_us=None if self.start_us is None else self.start_us[span_mask])
 
     def shard(self, nshards: int, rank: int) -> "SpanSet":
         """Traces whose trace_hash % nshards == rank."""
@@ -129,13 +138,14 @@ class SpanSet:
         remap[used] = np.arange(used.shape[0], dtype=np.uint16)
         return SpanSet([self.services[i] for i in used.tolist()], self.trace_ptr, self.trace_hash,
                        self.span_id, self.parent_span_id, remap[self.svc], self.flags,
-                       self.dur_us, self.trace_ids, self.unique_ids)
+                       self.dur_us, self.trace_ids, self.unique_ids, start_us=self.start_us)
 
     def take(self, order: np.ndarray, trace_ptr: np.ndarray) -> "SpanSet":
         """The spans in `order`, split into traces by `trace_ptr`."""
         return SpanSet(self.services, trace_ptr, self.trace_hash[order], self.span_id[order],
                        self.parent_span_id[order], self.svc[order], self.flags[order],
-                       self.dur_us[order])
+                       self.dur_us[order],
+                       start_us=None if self.start_us is None else self.start_us[order])
 
     @staticmethod
     def concat(sets: list["SpanSet"]) -> "SpanSet":
@@ -154,7 +164,9 @@ class SpanSet:
             ids = [t for s in sets for t in s.trace_ids]
         return SpanSet(list(services), ptr, cat("trace_hash"), cat("span_id"),
                        cat("parent_span_id"), cat("svc"), cat("flags"), cat("dur_us"), ids,
-                       all(s.unique_ids for s in sets))
+                       all(s.unique_ids for s in sets),
+                       start_us=(cat("start_us") if all(s.start_us is not None for s in sets)
+                                 else None))
 
 
 def edge_rows(n_services: int) -> int:
@@ -231,6 +243,62 @@ class EdgeTable:
             ws.extend(cnt[p, nz].tolist())
             row_ptr[p + 1] = len(cols)
         return row_ptr, np.asarray(cols, dtype=np.uint32), np.asarray(ws, dtype=np.float32)
+
+
+@dataclass
+class EdgeWindows:
+    """Per-window edge table of a span set with start times
+    (anomod_edge_windows_spans): window w covers starts in
+    [t0_us + w * step_us, t0_us + (w + 1) * step_us); rows as in EdgeTable."""
+
+    services: list[str]
+    t0_us: int
+    step_us: int
+    count: np.ndarray    # u64 [T, E]
+    errors: np.ndarray   # u64 [T, E]
+    sum_us: np.ndarray   # u64 [T, E]
+    max_us: np.ndarray   # u32 [T, E]; 0 for an empty cell
+    outside: int = 0     # spans that start before t0_us or at / after the last window's end
+
+    @property
+    def n_windows(self) -> int:
+        return int(self.count.shape[0])
+
+    @staticmethod
+    def empty(services: list[str], t0_us: int, step_us: int, n_windows: int) -> "EdgeWindows":
+        shape = (n_windows, edge_rows(len(services)))
+        return EdgeWindows(list(services), int(t0_us), int(step_us), np.zeros(shape, np.uint64),
+                           np.zeros(shape, np.uint64), np.zeros(shape, np.uint64),
+                           np.zeros(shape, np.uint32))
+
+    def matrix(self, min_count: int = 5):
+        """The table as a time-major series matrix for the EWMA/z kernels: the
+        active edges (non-zero total count, ascending row) give two f32
+        columns each, log2(1 + count) and log2(1 + sum_us / count) (NaN where
+        the window holds fewer than min_count spans of the edge), computed in
+        f64.  Series keys: ("edge_count" | "edge_mean_us", (("parent", name),
+        ("child", name))); timestamps are the window starts in epoch seconds."""
+        from .decode import MetricMatrix
+
+        S = len(self.services)
+        T = self.n_windows
+        active = np.nonzero(self.count.sum(axis=0))[0]
+        cnt = self.count[:, active].astype(np.float64)
+        tot = self.sum_us[:, active].astype(np.float64)
+        X = np.empty((T, 2 * active.shape[0]), np.float32)
+        X[:, 0::2] = np.log2(1.0 + cnt)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = np.where(self.count[:, active] >= max(int(min_count), 1),
+                            np.log2(1.0 + tot / cnt), np.nan)
+        X[:, 1::2] = mean
+        series = []
+        for r in active.tolist():
+            p, c = divmod(r, S)
+            name = "ROOT" if p == S else "ORPHAN" if p == S + 1 else self.services[p]
+            labels = (("parent", name), ("child", self.services[c]))
+            series += [("edge_count", labels), ("edge_mean_us", labels)]
+        ts = (self.t0_us + np.arange(T, dtype=np.float64) * self.step_us) / 1e6
+        return MetricMatrix(X, ts, series)
 
 
 @dataclass

@@ -33,7 +33,8 @@ struct UpItem {
 
 enum Stage { kStageEdgeAgg = 0, kStageEdgeFinal = 1, kStageEdgeReduce = 2, kStageEwma = 3,
              kStagePagerank = 4, kStageTraceStruct = 5, kStageSegments = 6, kStageSummary = 7,
-             kStageGroup = 8, kNumStages = 9 };
+             kStageGroup = 8, kStageEdgeWindows = 9, kStageEdgeWindowKernel = 10,
+             kNumStages = 11 };
 
 // Host wall-clock slots (anomod_ctx_host_ms): the last occurrence of each
 // one-off setup step, or of a call phase the stage events cannot see.
@@ -77,8 +78,8 @@ struct anomod_ctx {
   // scripts/r06/time_cold2.py), so a call reuses its slot instead of
   // allocating and freeing; released with the ctx, or when an allocation
   // would otherwise fail (release_scratch).
-  void* scratch[4] = {};
-  size_t scratch_bytes[4] = {};
+  void* scratch[5] = {};
+  size_t scratch_bytes[5] = {};
   // Cached device workspace for the edge table.
   void* d_table = nullptr;
   size_t table_bytes = 0;
@@ -126,6 +127,7 @@ struct anomod_spans {
   uint32_t* svc_flags = nullptr;  // svc | flags << 16 (one 4-B load per span)
   uint32_t* dur_us = nullptr;
   uint64_t* trace_ptr = nullptr;  // [n_traces + 1]
+  uint64_t* start_us = nullptr;   // [n_spans] epoch microseconds, or none (edge_windows.hip)
 };
 
 #define ANOMOD_HIP(ctx, expr)                                                               \
@@ -224,10 +226,18 @@ void free_uploader(anomod_ctx* ctx);
 // histogram-form hint (read, and updated with what the run learned).
 int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uint32_t S,
                            int8_t* hist_form, anomod_edge_table* out);
+// Per-span edge keys of a grouped set (edge_agg.hip): keys[i] = edge row << 32
+// | dur_us by span position, from the aggregation kernels' own walk and parent
+// rule (order probe, chunk walk per launch cut, long-trace pass), queued on
+// the ctx stream.  ws: device words the walk uses, span_edge_keys_ws_bytes
+// of them, 8-B aligned.
+size_t span_edge_keys_ws_bytes(const anomod_spans* s);
+int span_edge_keys(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, unsigned long long* keys,
+                   unsigned long long* ws);
 // Grow-only device workspace owned by the ctx.
 int ensure_table(anomod_ctx* ctx, size_t bytes);
 enum ScratchSlot { kScratchQuantiles = 0, kScratchTraceStruct = 1, kScratchTsLong = 2,
-                   kScratchUpload = 3, kNumScratch = 4 };
+                   kScratchUpload = 3, kScratchEdgeWindows = 4, kNumScratch = 5 };
 // *out = the slot's block of at least `bytes` (grown when smaller; on
 // failure the slots outside `keep` (a mask; this slot is always kept) are
 // released and the allocation retried once).

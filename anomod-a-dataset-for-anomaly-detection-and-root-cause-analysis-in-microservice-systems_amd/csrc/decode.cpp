@@ -54,6 +54,7 @@ struct anomod_decoded {
   std::vector<uint64_t> trace_hash, span_id, parent;
   std::vector<uint16_t> svc, flags;
   std::vector<uint32_t> dur;
+  std::vector<uint64_t> start_us;  // epoch microseconds, 0 = none (anomod_decoded_start_us)
   bool dup_ids = false;  // some trace holds a span id twice (anomod_decoded_unique_ids)
 };
 
@@ -447,6 +448,24 @@ uint32_t clamp_u32(const Dom& d, uint32_t id) {
   return (uint32_t)v;
 }
 
+// A span's start time: the JSON value when it is a non-negative integer
+// (digits only: no sign, fraction or exponent; not a string or a bool) times
+// `mult`, 0 when it is anything else or the product does not fit a u64.
+uint64_t start_time_us(const Dom& d, uint32_t id, uint64_t mult) {
+  if (id == kNone || d.at(id).type != J_NUM) return 0;
+  const std::string_view r = d.raw(id);
+  if (r.empty()) return 0;
+  uint64_t v = 0;
+  for (char c : r) {
+    if (c < '0' || c > '9') return 0;
+    const uint64_t dgt = (uint64_t)(c - '0');
+    if (v > (~0ull - dgt) / 10) return 0;
+    v = v * 10 + dgt;
+  }
+  if (mult > 1 && v > ~0ull / mult) return 0;
+  return v * mult;
+}
+
 bool truthy_error_tag(const Dom& d, uint32_t id) {
   if (id == kNone) return false;
   const Node& nd = d.at(id);
@@ -562,6 +581,7 @@ void jaeger_trace(const Dom& d, uint32_t tr, anomod_decoded* out, Names& names,
       out->parent.push_back(parent);
       out->flags.push_back(error ? ANOMOD_FLAG_ERROR : 0);
       out->dur.push_back(clamp_u32(d, d.get(sp, "duration")));
+      out->start_us.push_back(start_time_us(d, d.get(sp, "startTime"), 1));
     }
   }
   // span ids unique inside the trace? (lets the GPU parent scans run from
@@ -614,6 +634,7 @@ void skywalking_trace(const Dom& d, uint32_t tr, anomod_decoded* out, Names& nam
     long double us = ok ? (b - a) * 1000.0L : 0;
     if (us < 0) us = 0;
     out->dur.push_back(us > 4294967295.0L ? 0xFFFFFFFFu : (uint32_t)us);
+    out->start_us.push_back(start_time_us(d, sa, 1000));
     out->flags.push_back(truthy(d, d.get(sp, "is_error")) ? ANOMOD_FLAG_ERROR : 0);
   }
   out->trace_ptr.push_back(out->span_id.size());
@@ -836,6 +857,7 @@ bool decode_parallel(const char* json, size_t len, int kind, anomod_decoded* out
   out->parent.reserve(ns);
   out->flags.reserve(ns);
   out->dur.reserve(ns);
+  out->start_us.reserve(ns);
   out->trace_ptr.reserve(nt + 1);
   for (int t = 0; t < threads; ++t) {
     const uint64_t base = out->span_id.size();
@@ -845,6 +867,7 @@ bool decode_parallel(const char* json, size_t len, int kind, anomod_decoded* out
     app(out->parent, part[t].parent);
     app(out->flags, part[t].flags);
     app(out->dur, part[t].dur);
+    app(out->start_us, part[t].start_us);
     out->dup_ids = out->dup_ids || part[t].dup_ids;
     for (size_t k = 1; k < part[t].trace_ptr.size(); ++k)
       out->trace_ptr.push_back(base + part[t].trace_ptr[k]);
@@ -972,6 +995,15 @@ int anomod_decoded_columns(const anomod_decoded* d, const anomod_span_soa_out* d
   cp(dst->flags, d->flags.data(), n * 2);
   cp(dst->dur_us, d->dur.data(), n * 4);
   cp(trace_ptr, d->trace_ptr.data(), d->trace_ptr.size() * 8);
+  return ANOMOD_OK;
+}
+
+int anomod_decoded_start_us(const anomod_decoded* d, uint64_t* dst) {
+  if (!d || !dst) {
+    anomod::set_error(nullptr, "anomod_decoded_start_us: NULL argument");
+    return ANOMOD_EINVAL;
+  }
+  if (!d->start_us.empty()) std::memcpy(dst, d->start_us.data(), d->start_us.size() * 8);
   return ANOMOD_OK;
 }
 

@@ -2037,6 +2037,42 @@ int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uin
   return ANOMOD_OK;
 }
 
+// ws words: [0] dynamic-tail counter, [1..3] long-trace counters, [4..5] order
+// probe, [32..] long-trace list.
+size_t span_edge_keys_ws_bytes(const anomod_spans* s) { return 256 + big_capacity(s) * 8; }
+
+int span_edge_keys(anomod_ctx* ctx, const anomod_spans* spans, uint32_t S,
+                   unsigned long long* keys, unsigned long long* ws) {
+  if (!spans->n_spans || !spans->n_traces) return ANOMOD_OK;
+  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
+  Table tab{};
+  tab.keys = keys;
+  tab.ctr = ws;
+  tab.big = ws + 1;
+  tab.big_list = ws + 32;
+  if (int rc = probe_order(ctx, spans, ws + 4)) return rc;
+  KernelFn fn = use_unique(spans) ? edge_agg_kernel<kHtKeys, kStHbm, true>
+                                  : edge_agg_kernel<kHtKeys, kStHbm, false>;
+  int per_cu = 0;
+  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                      &per_cu, reinterpret_cast<const void*>(fn), kThreads, 0));
+  const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
+  std::vector<uint64_t> cuts;
+  if (int rc = span_launch_cuts(ctx, spans, max_launch_spans(), cuts)) return rc;
+  ANOMOD_HIP(ctx, hipMemsetAsync(ws, 0, 32, ctx->stream));  // ctr + big counters
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+    if (k > 0) ANOMOD_HIP(ctx, hipMemsetAsync(ws, 0, 8, ctx->stream));
+    Table tk = tab;
+    tk.t_base = cuts[k];
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, spans->span_id,
+                       spans->parent_span_id, spans->svc_flags, spans->dur_us,
+                       spans->trace_ptr + cuts[k], cuts[k + 1] - cuts[k], S, E, tk);
+    ANOMOD_HIP(ctx, hipGetLastError());
+  }
+  if (big_capacity(spans)) ANOMOD_HIP(ctx, (launch_big<kHtKeys, kStHbm>(ctx, spans, S, E, tab)));
+  return ANOMOD_OK;
+}
+
 }  // namespace anomod
 
 using namespace anomod;
@@ -2231,9 +2267,8 @@ int anomod_edge_quantiles_exact(anomod_ctx* ctx, const anomod_spans* spans, uint
   const uint64_t n = spans->n_spans;
   int kbits = 1;
   while ((uint64_t)E >> kbits) ++kbits;
-  // One workspace: keys | sorted keys | sort temp | q | out | count | ctr +
-  // long-trace counters | long-trace list
-  const uint64_t big_cap = big_capacity(spans);
+  // One workspace: keys | sorted keys | sort temp | q | out | count | the key
+  // walk's words (span_edge_keys: counters | long-trace list)
   const size_t sort_tmp = n ? radix_temp_bytes(n) : 0;
   auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
   const size_t b_keys = al(n * 8), b_tmp = al(sort_tmp), b_q = al(nq * 4), b_out = al(E * nq * 8ull),
@@ -2241,7 +2276,8 @@ int anomod_edge_quantiles_exact(anomod_ctx* ctx, const anomod_spans* spans, uint
   // (the ctx's scratch slot: reused by the next call instead of freed)
   char* w = nullptr;
   if (int rc = ensure_scratch(ctx, kScratchQuantiles,
-                              2 * b_keys + b_tmp + b_q + b_out + b_cnt + 256 + big_cap * 8,
+                              2 * b_keys + b_tmp + b_q + b_out + b_cnt +
+                                  span_edge_keys_ws_bytes(spans),
                               reinterpret_cast<void**>(&w)))
     return rc;
   auto* keys = reinterpret_cast<unsigned long long*>(w);
@@ -2256,34 +2292,8 @@ int anomod_edge_quantiles_exact(anomod_ctx* ctx, const anomod_spans* spans, uint
   if (e == hipSuccess && n && spans->n_traces) {
     // per-span (edge, latency) keys from the aggregation kernel's own walk and
     // parent rule, then one radix sort over edge|dur
-    Table tab{};
-    tab.keys = keys;
-    tab.ctr = d_ctr;
-    tab.big = d_ctr + 1;
-    tab.big_list = d_ctr + 32;
-    rc = probe_order(ctx, spans, d_ctr + 4);
-    KernelFn fn = use_unique(spans) ? edge_agg_kernel<kHtKeys, kStHbm, true>
-                                    : edge_agg_kernel<kHtKeys, kStHbm, false>;
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(fn),
-                                                     kThreads, 0);
-    const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    std::vector<uint64_t> cuts;
-    if (e == hipSuccess && rc == ANOMOD_OK) rc = span_launch_cuts(ctx, spans, max_launch_spans(), cuts);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ctr, 0, 32, ctx->stream);  // ctr + big counters
-    for (size_t k = 0; e == hipSuccess && rc == ANOMOD_OK && k + 1 < cuts.size(); ++k) {
-      if (k > 0) e = hipMemsetAsync(d_ctr, 0, 8, ctx->stream);
-      if (e != hipSuccess) break;
-      Table tk = tab;
-      tk.t_base = cuts[k];
-      hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, spans->span_id,
-                         spans->parent_span_id, spans->svc_flags, spans->dur_us,
-                         spans->trace_ptr + cuts[k], cuts[k + 1] - cuts[k], S, E, tk);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && rc == ANOMOD_OK && big_cap)
-      e = launch_big<kHtKeys, kStHbm>(ctx, spans, S, E, tab);
-    if (e == hipSuccess && rc == ANOMOD_OK)
+    rc = span_edge_keys(ctx, spans, S, keys, d_ctr);
+    if (rc == ANOMOD_OK)
       e = radix_sort_u64(reinterpret_cast<const uint64_t*>(keys),
                          reinterpret_cast<uint64_t*>(sorted), n, 0, 32 + kbits, tmp, sort_tmp,
                          ctx->stream);

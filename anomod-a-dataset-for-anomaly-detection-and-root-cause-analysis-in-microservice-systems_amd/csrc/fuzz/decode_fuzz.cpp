@@ -76,6 +76,8 @@ int run(const Seed& sd, const std::string& data) {
     std::vector<uint32_t> dur(ns);
     anomod_span_soa_out o{th.data(), sid.data(), pid.data(), svc.data(), fl.data(), dur.data()};
     anomod_decoded_columns(d, &o, ptr.data());
+    std::vector<uint64_t> start(ns);
+    anomod_decoded_start_us(d, start.data());
     for (uint32_t i = 0; i < nsv; ++i) (void)strlen(anomod_decoded_service(d, i));
     anomod_decoded_free(d);
     return 1;

@@ -396,7 +396,7 @@ void free_spans(anomod_spans* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
   void* ptrs[] = {s->trace_hash, s->span_id, s->parent_span_id, s->svc_flags, s->dur_us,
-                  s->trace_ptr};
+                  s->trace_ptr, s->start_us};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete s;

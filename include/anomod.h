@@ -119,7 +119,9 @@ int anomod_ctx_synchronize(anomod_ctx* ctx);
  * 2 = edge all-reduce, 3 = ewma kernel, 4 = pagerank iterations,
  * 5 = trace-structure kernel, 6 = segment-summary kernel,
  * 7 = value summary (select + sort + sum + picks),
- * 8 = trace grouping of an ungrouped span set (radix passes + copy + trace_ptr). */
+ * 8 = trace grouping of an ungrouped span set (radix passes + copy + trace_ptr),
+ * 9 = edge-window pass (per-span edge keys + the window kernel),
+ * 10 = the window kernel of stage 9 alone.                                  */
 int anomod_ctx_stage_ms(const anomod_ctx* ctx, int stage, double* ms);
 /* Host wall milliseconds of the last occurrence of a one-off setup step or of
  * a call phase the stage events above cannot see, and how many times it
@@ -179,6 +181,24 @@ int anomod_spans_info(const anomod_spans* spans, uint64_t* n_spans, uint64_t* n_
 int anomod_spans_download(anomod_ctx* ctx, const anomod_spans* spans,
                           const anomod_span_soa_out* dst, uint64_t* trace_ptr);
 int anomod_spans_free(anomod_spans* spans);
+/* Optional start-time column of a set: epoch microseconds per span, by span
+ * position (Jaeger startTime, jaeger_to_csv.py:41-43; SkyWalking
+ * start_timestamp_ms * 1000) — the time axis of anomod_edge_windows_spans.
+ * A set has none until set_start_us / fill_start_synthetic gives it one, and
+ * the sets made by anomod_spans_group, anomod_spans_shuffle and
+ * anomod_spans_generate carry none (a regrouped copy does not inherit it).
+ * get_start_us: ANOMOD_ESTATE when the set has none.                        */
+int anomod_spans_set_start_us(anomod_ctx* ctx, anomod_spans* spans,
+                              const uint64_t* start_us /* [n_spans], host */);
+int anomod_spans_has_start_us(const anomod_spans* spans, int* has);
+int anomod_spans_get_start_us(anomod_ctx* ctx, const anomod_spans* spans, uint64_t* dst);
+/* Synthetic start times, generated on the device (grouped sets only): span i
+ * at position pos of trace t gets
+ *   t0_us + (t * period_us) / n_traces + pos * gap_us
+ * (u64 arithmetic) — traces spread evenly over one period, in order.
+ * ANOMOD_EINVAL unless n_traces * period_us < 2^63.                         */
+int anomod_spans_fill_start_synthetic(anomod_ctx* ctx, anomod_spans* spans, uint64_t t0_us,
+                                      uint64_t period_us, uint64_t gap_us);
 
 /* ---- ungrouped span sets (BASELINE.json north_star (2)) ------------------
  * Spans that arrive interleaved across traces — the Elasticsearch path of
@@ -274,6 +294,10 @@ int anomod_decoded_unique_ids(const anomod_decoded* d, int* unique);
 const char* anomod_decoded_service(const anomod_decoded* d, uint32_t i);
 int anomod_decoded_columns(const anomod_decoded* d, const anomod_span_soa_out* dst,
                            uint64_t* trace_ptr /* [n_traces + 1] */);
+/* Start time of every span in epoch microseconds: Jaeger startTime, SkyWalking
+ * start_timestamp_ms * 1000; 0 when the value is missing, negative, not an
+ * integer, or does not fit a u64.                                          */
+int anomod_decoded_start_us(const anomod_decoded* d, uint64_t* dst /* [n_spans] */);
 int anomod_decoded_free(anomod_decoded* d);
 /* The 64-bit id hash of the decoders (xxh64, seed 0; 0 maps to 1).       */
 uint64_t anomod_hash64(const char* s, uint64_t len);
@@ -358,6 +382,29 @@ int anomod_edge_aggregate_ungrouped(anomod_ctx* ctx, const anomod_spans* spans,
  * [0, 99], nq <= 16.                                                        */
 int anomod_edge_quantiles_exact(anomod_ctx* ctx, const anomod_spans* spans, uint32_t n_services,
                                 const uint32_t* q_pct, uint32_t nq, double* out, uint64_t* count);
+/* Per-window edge table of a grouped set with a start-time column: the edge
+ * of a span is the row anomod_edge_aggregate_spans puts it in, its window
+ *   w = (start_us - t0_us) / step_us   (integer floor)
+ * and cell w * E + row accumulates count, errors, latency sum and max.  A
+ * span with start_us < t0_us or w >= n_windows is counted in `outside` and
+ * in no cell.  Every result is an integer, bit-exact for any launch
+ * geometry.  A set without a start column gives ANOMOD_ESTATE; n == 0 gives
+ * zeros.  The call is rank-local: no collective runs even with a
+ * communicator attached (the cells are integers: a caller sums the ranks'
+ * tables itself, max for max_us).                                          */
+typedef struct {
+  uint32_t n_services;   /* in : S; E = (S + 2) * S as in anomod_edge_table      */
+  uint32_t n_windows;    /* in : T in [1, 65536], T * E <= 2^24, else EINVAL      */
+  uint64_t t0_us;        /* in                                                   */
+  uint64_t step_us;      /* in : >= 1                                            */
+  uint64_t* count;       /* [T * E], cell = w * E + edge row; each may be NULL   */
+  uint64_t* errors;
+  uint64_t* sum_us;
+  uint32_t* max_us;      /* 0 for an empty cell                                  */
+  uint64_t outside;      /* out: spans with start < t0 or start >= t0 + T * step */
+} anomod_edge_windows;
+int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                              anomod_edge_windows* out);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
