@@ -238,13 +238,12 @@ class Context:
     def group_info(self) -> dict:
         """How the last grouping ran: path ("bucket" / "join": the bucket
         scatters then the ungrouped aggregation's per-bucket hash join /
-        "fused-sort": the same scatters then the sorting bucket kernels' edge
-        records (ANOMOD_FUSED_JOIN=0) / "lsd"),
+        "lsd"),
         scatter levels or radix passes, and the key bits they sorted on."""
         p, lv, b = C.c_int(), C.c_int(), C.c_int()
         self._check(self._lib.anomod_ctx_group_info(self.handle, C.byref(p), C.byref(lv),
                                                     C.byref(b)))
-        return {"path": {1: "bucket", 2: "join", 3: "fused-sort"}.get(p.value, "lsd"), "levels": lv.value,
+        return {"path": {1: "bucket", 2: "join"}.get(p.value, "lsd"), "levels": lv.value,
                 "bits": b.value}
 
     # -- multi-GPU

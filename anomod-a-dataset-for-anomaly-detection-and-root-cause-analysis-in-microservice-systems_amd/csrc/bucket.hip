@@ -43,19 +43,6 @@ namespace anomod {
 namespace {
 
 using chunk::wave_sync;
-// Experiment-only builds (never set in the shipped library):
-//  2 = level A stores nothing, then the LSD path groups (timing of level A's
-//      loads and ranking only);
-//  4 = nontemporal record stores in level A;
-//  8 = small bucket kernel: no record gathers (records made from the pairs);
-// 16 = small bucket kernel: no column / trace-start stores;
-// 32 = small bucket kernel: no in-LDS ranking (arrival order kept).
-// (8 / 16 / 32 give wrong groupings: timing only.)
-
-
-#ifndef ANOMOD_BK_ABL
-#define ANOMOD_BK_ABL 0
-#endif
 constexpr int kWv = 64;
 constexpr int kBThreads = 1024;                // scatter workgroup
 constexpr int kBWaves = kBThreads / kWv;       // 16
@@ -63,10 +50,7 @@ constexpr int kBWaves = kBThreads / kWv;       // 16
 // workgroups per CU (one tile's loads and ranking overlap the other's
 // scattered stores): grouping 62.7 -> 58.7 ms at 2^27 SN traces against
 // 4096-record tiles at one workgroup per CU (gpurun_out/r4d_aper2.log).
-#ifndef ANOMOD_BK_APER
-#define ANOMOD_BK_APER 2
-#endif
-constexpr int kBPer = ANOMOD_BK_APER;          // records per thread
+constexpr int kBPer = 2;                       // records per thread
 constexpr int kBTile = kBThreads * kBPer;      // 2048 records per level-A tile
 constexpr int kPPer = 16;                      // pairs per thread (level B)
 constexpr int kPTile = kBThreads * kPPer;      // 16384 pairs per level-B tile (128 KiB)
@@ -76,15 +60,8 @@ constexpr int kScanRows = 256;                 // tiles per block of the tile sc
 constexpr int kScanB = 16;                     // loads in flight per serial scan step
 constexpr int kSubBits = 9;                    // per-bucket split before the key compare
 constexpr int kSub = 1 << kSubBits;
-#ifndef ANOMOD_BK_SPER
-#define ANOMOD_BK_SPER 4
-#endif
-constexpr int kSmallW = 512, kSmallPer = ANOMOD_BK_SPER;  // per-bucket kernel: 2048 spans
+constexpr int kSmallW = 512, kSmallPer = 4;    // per-bucket kernel: 2048 spans
 constexpr int kBigW = 1024, kBigPer = 8;       // oversized buckets: 8192 spans
-#ifndef ANOMOD_BK_RANK
-#define ANOMOD_BK_RANK 0  // small bucket kernel: 0 = stable split, 1 = atomic slots + compare rank
-#endif
-constexpr bool kRankAtomic = ANOMOD_BK_RANK != 0;
 constexpr int kDChunk = 4096;                  // entries per partial sum of the trace-count scan
 
 // Exclusive scan of one value per thread across a workgroup of NW waves;
@@ -343,7 +320,6 @@ __device__ inline uint64_t make_pair(uint64_t k, int da, uint64_t g) {
 __global__ __launch_bounds__(kBThreads) void bk_scatter_a_kernel(
     SoaIn sin, GRec* __restrict__ aout, uint64_t* __restrict__ pout, uint64_t n, int da,
     const uint32_t* __restrict__ toff, uint32_t nx) {
-  constexpr bool kNoStore = (ANOMOD_BK_ABL & 2) != 0;
   static_assert(kBWaves * kNDMax * 2 <= kBTile * 32, "counters fit under the stage");
   union Lds {
     uint4 stage[2 * kBTile];              // 128 KiB: the tile's records in digit order
@@ -435,7 +411,6 @@ __global__ __launch_bounds__(kBThreads) void bk_scatter_a_kernel(
     }
   }
   __syncthreads();
-  if constexpr (kNoStore) return;
   // 16-B chunks in staged order: chunk c is half (c & 1) of staged record c / 2;
   // the lane holding a record's first half also writes its pair
   const uint64_t nch = 2 * nvalid;
@@ -449,12 +424,7 @@ __global__ __launch_bounds__(kBThreads) void bk_scatter_a_kernel(
       const uint64_t k = mix64(((uint64_t)x0.y << 32) | x0.x);
       const uint32_t dd = (uint32_t)(k >> shift) & (uint32_t)(nd - 1);
       const uint64_t g = (uint64_t)gbase[dd] + (p - tstart[dd]);
-      if constexpr ((ANOMOD_BK_ABL & 4) != 0) {
-        using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
-        __builtin_nontemporal_store(u32x4{x.x, x.y, x.z, x.w},
-                                    reinterpret_cast<u32x4*>(aout) + 2 * g + (c & 1u));
-      } else
-        reinterpret_cast<uint4*>(aout)[2 * g + (c & 1u)] = x;
+      reinterpret_cast<uint4*>(aout)[2 * g + (c & 1u)] = x;
       if (!(c & 1u)) pout[g] = make_pair(k, da, g);
     }
   }
@@ -701,7 +671,7 @@ __global__ __launch_bounds__(kBThreads) void bk_scatter_b_rec_kernel(
 }
 
 // ---- one bucket in (k, arrival) order ---------------------------------------
-template <int W, int PER, bool EDGE = false>
+template <int W, int PER>
 struct BucketLds {
   static constexpr int kCap = W * PER, kNW = W / kWv;
   static_assert(kNW * kSub >= kCap, "trace starts fit over the sub-digit counters");
@@ -717,17 +687,12 @@ struct BucketLds {
     Pre pre;
   } u;
   uint16_t sfinal[kCap];          // final position of every arrival position
-  uint16_t ssvc[EDGE ? kCap : 1]; // edge records: services by final position
+  // 4 bytes where the removed edge form's ssvc[1] and its alignment stood: wsum
+  // and flag keep their offsets (the big kernel's code does not move), and
+  // sizeof, which bucket_sort_one's `if constexpr` for bucket_huge reads, stays
+  uint32_t pad;
   uint32_t wsum[kNW];
   uint32_t flag;
-};
-
-// Edge-record output of the fused ungrouped aggregation: per span, its
-// (parent service row * S + service) edge << 33 | error << 32 | duration,
-// the parent found in the span's trace by the first-match rule.
-struct EdgeOut {
-  uint64_t* rec;  // [n], by grouped position
-  uint32_t S;
 };
 
 // A bucket beyond the large kernel (a trace of thousands of spans, or two
@@ -858,92 +823,11 @@ __device__ void bucket_huge(unsigned char* lds, uint32_t c, uint32_t a0, uint32_
   if (tid == 0) dcnt[c] = d;
 }
 
-// The bucket in final order -> one edge record per span (fused ungrouped
-// aggregation): span ids and services staged in LDS by final position, each
-// trace's bounds from its start flags, the parent found by the first-match
-// scan over the trace (the order jaeger_to_csv.py:34-38 /
-// trace_collector.py:424-443 see: arrival order inside the trace).
-template <int W, int PER, bool EDGE, int R>
-__device__ void bucket_edges(BucketLds<W, PER, EDGE>& L, uint32_t a0, uint32_t m,
-                             const uint64_t (&k)[PER], const bool (&v)[PER], const uint4 (&ra)[R],
-                             const uint4 (&rb)[R], const GRec* __restrict__ rec, EdgeOut eo) {
-  constexpr int kNW = W / kWv;
-  constexpr bool REG = R == PER;
-  auto& P = L.u.pre;
-  const int tid = threadIdx.x, lane = tid & (kWv - 1), w = tid / kWv;
-  uint16_t* tord = P.sorig;            // trace ordinal of every final position
-  uint16_t* tsf = &P.wcnt[0][0];       // first final position of every trace
-  // ordinals of the trace starts (thread tid: final positions tid * PER + j)
-  uint32_t cnt = 0;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const uint32_t f = (uint32_t)(tid * PER + j);
-    cnt += f < m ? P.sflag[f] : 0u;
-  }
-  uint32_t nt;
-  uint32_t ord = block_excl_scan<kNW>(cnt, L.wsum, &nt);  // its barriers order sflag / skey
-  uint4 x0[PER], x1[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const uint32_t p = (uint32_t)(w * (PER * kWv) + j * kWv + lane);
-    if constexpr (REG) {
-      x0[j] = ra[j];
-      x1[j] = rb[j];
-    } else {
-      const uint4* q = reinterpret_cast<const uint4*>(rec + (uint32_t)k[j]);
-      x0[j] = v[j] ? q[0] : make_uint4(0, 0, 0, 0);
-      x1[j] = v[j] ? q[1] : make_uint4(0, 0, 0, 0);
-    }
-    if (v[j]) {
-      const uint32_t f = L.sfinal[p];
-      P.skey[f] = ((uint64_t)x0[j].w << 32) | x0[j].z;  // span id
-      L.ssvc[f] = (uint16_t)x1[j].z;                     // service
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const uint32_t f = (uint32_t)(tid * PER + j);
-    if (f < m) {
-      if (P.sflag[f]) tsf[ord++] = (uint16_t)f;
-      tord[f] = (uint16_t)(ord - 1u);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    if (!v[j]) continue;
-    const uint32_t p = (uint32_t)(w * (PER * kWv) + j * kWv + lane);
-    const uint32_t f = L.sfinal[p], t = tord[f];
-    const uint32_t a = tsf[t], b = t + 1u < nt ? tsf[t + 1u] : m;
-    const uint64_t pid = ((uint64_t)x1[j].y << 32) | x1[j].x;
-    uint32_t prow = eo.S;  // ROOT: no parent reference
-    if (pid != 0ull) {
-      prow = eo.S + 1u;  // ORPHAN unless the trace holds the reference
-      for (uint32_t q0 = a; q0 < b; q0 += 4) {  // first match, 4 ids per LDS round trip
-        uint64_t id[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) id[u] = P.skey[q0 + u < b ? q0 + u : a];
-        int hit = -1;
-#pragma unroll
-        for (int u = 3; u >= 0; --u)
-          if (q0 + u < b && id[u] == pid) hit = u;
-        if (hit >= 0) {
-          prow = L.ssvc[q0 + hit];
-          break;
-        }
-      }
-    }
-    const uint32_t svc = x1[j].z & 0xFFFFu, fl = x1[j].z >> 16;
-    eo.rec[a0 + f] = ((uint64_t)(prow * eo.S + svc) << 33) |
-                     ((uint64_t)((fl & ANOMOD_FLAG_ERROR) ? 1u : 0u) << 32) | x1[j].w;
-  }
-}
-
 // Two traces of a bucket whose keys agree in every bit the pairs carry: the
 // bucket ranked by (full key, arrival) instead (rare: O(m^2) compares by
 // every thread).  Every thread calls it (barriers).
-template <int W, int PER, bool EDGE>
-__device__ void bucket_rerank_exact(BucketLds<W, PER, EDGE>& L, uint32_t m,
+template <int W, int PER>
+__device__ void bucket_rerank_exact(BucketLds<W, PER>& L, uint32_t m,
                                     const uint64_t (&fk)[PER], const bool (&v)[PER]) {
   auto& P = L.u.pre;
   const int tid = threadIdx.x, lane = tid & (kWv - 1), w = tid / kWv;
@@ -973,8 +857,8 @@ __device__ void bucket_rerank_exact(BucketLds<W, PER, EDGE>& L, uint32_t m,
 
 // The bucket's final order in LDS (sfinal: arrival -> final position; sflag:
 // trace starts by final position).
-template <int W, int PER, bool EDGE, int R>
-__device__ void bucket_rank(BucketLds<W, PER, EDGE>& L, uint32_t a0, uint32_t m,
+template <int W, int PER, int R>
+__device__ void bucket_rank(BucketLds<W, PER>& L, uint32_t a0, uint32_t m,
                             const GRec* __restrict__ rec, int kshift, const uint64_t (&k)[PER],
                             const bool (&v)[PER], const uint4 (&ra)[R], const uint4 (&rb)[R]) {
   constexpr int kCap = W * PER, kNW = W / kWv;
@@ -1107,107 +991,14 @@ __device__ void bucket_rank(BucketLds<W, PER, EDGE>& L, uint32_t a0, uint32_t m,
     const uint32_t f = (uint32_t)(tid + j * W);
     clash |= f > 0 && f < m && !P.sflag[f] && P.skey[f] != P.skey[f - 1];
   }
-  if constexpr ((ANOMOD_BK_ABL & 8) != 0) clash = false;  // timing: keys are not the records'
-  if (__syncthreads_or(clash)) bucket_rerank_exact<W, PER, EDGE>(L, m, fk, v);
-
-}
-
-// Small-kernel ranking without the stable split (ANOMOD_BK_RANK=1): each span
-// takes a slot in its sub-bucket with one LDS atomic (any order), the
-// sub-bucket starts come from one block scan, and a span's final position is
-// a + #{pairs of its sub-bucket below its own} — pairs are distinct and order
-// by (key bits, arrival), so this is the stable order however the slots were
-// taken.  The compare loop is O(s) per span, so a bucket holding a sub-bucket
-// of more than kLongSub spans (a long trace) returns false and goes to the
-// large kernel's stable split.  The full-key check rides along: spans with
-// equal pair keys must have equal low 32 bits of k (the bucket and the pair
-// fix the other da + 32 >= 33), else the bucket is re-ranked exactly.
-constexpr uint32_t kLongSub = 128;
-template <int W, int PER, bool EDGE, int R>
-__device__ bool bucket_rank_atomic(BucketLds<W, PER, EDGE>& L, uint32_t m, int kshift,
-                                   const uint64_t (&k)[PER], const bool (&v)[PER],
-                                   const uint4 (&ra)[R]) {
-  static_assert(R == PER, "records in registers");
-  constexpr int kCap = W * PER, kNW = W / kWv;
-  static_assert(kNW * kSub * 2 >= kCap * 4, "low key words fit over the wave counters");
-  static_assert(W == kSub, "one thread per sub-digit");
-  auto& P = L.u.pre;
-  uint32_t* cnt = P.mixed;                                      // [kSub] spans per sub-bucket
-  uint32_t* sfk = reinterpret_cast<uint32_t*>(&P.wcnt[0][0]);  // [kCap] low key word, staged
-  const int tid = threadIdx.x, lane = tid & (kWv - 1), w = tid / kWv;
-  uint64_t fk[PER];
-  uint32_t e[PER], o[PER];
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    fk[j] = mix64(((uint64_t)ra[j].y << 32) | ra[j].x);
-    e[j] = (uint32_t)(k[j] >> kshift) & (kSub - 1);
-  }
-  cnt[tid] = 0u;
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < PER; ++j) o[j] = v[j] ? atomicAdd(&cnt[e[j]], 1u) : 0u;
-  __syncthreads();
-  const uint32_t tot = cnt[tid];
-  uint32_t all;
-  const uint32_t pre = block_excl_scan<kNW>(tot, L.wsum, &all);
-  P.tstart[tid] = pre;
-  if (tid == 0) P.tstart[kSub] = m;
-  if (__syncthreads_or(tot > kLongSub)) return false;  // (also orders tstart)
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    if (v[j]) {
-      const uint32_t sp = P.tstart[e[j]] + o[j];
-      P.skey[sp] = k[j];
-      sfk[sp] = (uint32_t)fk[j];
-      P.sorig[sp] = (uint16_t)(w * (PER * kWv) + j * kWv + lane);
-    }
-  }
-  __syncthreads();
-  bool clash = false;
-#pragma unroll
-  for (int j = 0; j < PER; ++j) {
-    const uint32_t sp = (uint32_t)(tid + j * W);
-    if (sp < m) {
-      const uint64_t kp = P.skey[sp];
-      const uint32_t fp = sfk[sp];
-      const uint32_t ee = (uint32_t)(kp >> kshift) & (kSub - 1);
-      const uint32_t a = P.tstart[ee], b = P.tstart[ee + 1];
-      uint32_t rank = 0, first = 1;
-      if (b - a > 1u) {
-        for (uint32_t q0 = a; q0 < b; q0 += 4) {  // 4 pairs per step: one LDS round trip
-          uint64_t kq[4];
-          uint32_t fq[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const uint32_t q = q0 + t < b ? q0 + t : a;
-            kq[t] = P.skey[q];
-            fq[t] = sfk[q];
-          }
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const bool in = q0 + t < b;
-            const bool below = in && kq[t] < kp;  // pairs are distinct
-            const bool same = in && (kq[t] >> 32) == (kp >> 32);
-            rank += below ? 1u : 0u;
-            first &= (below && same) ? 0u : 1u;
-            clash |= same && fq[t] != fp;
-          }
-        }
-      }
-      const uint32_t f = a + rank;
-      P.sflag[f] = (uint8_t)first;
-      L.sfinal[P.sorig[sp]] = (uint16_t)f;
-    }
-  }
-  if (__syncthreads_or(clash)) bucket_rerank_exact<W, PER, EDGE>(L, m, fk, v);
-  return true;
+  if (__syncthreads_or(clash)) bucket_rerank_exact<W, PER>(L, m, fk, v);
 }
 
 // The bucket in final order out: its grouped columns (records by final
 // position), its trace starts over the bucket's own pairs (pin[a0 +
 // ordinal], read before) and its trace count dcnt[c].
-template <int W, int PER, bool EDGE, int R>
-__device__ void bucket_emit(BucketLds<W, PER, EDGE>& L, uint32_t c, uint32_t a0, uint32_t m,
+template <int W, int PER, int R>
+__device__ void bucket_emit(BucketLds<W, PER>& L, uint32_t c, uint32_t a0, uint32_t m,
                             uint64_t* __restrict__ pin, const GRec* __restrict__ rec, SoaOut out,
                             uint32_t* __restrict__ dcnt, const uint64_t (&k)[PER],
                             const bool (&v)[PER], const uint4 (&ra)[R], const uint4 (&rb)[R]) {
@@ -1248,10 +1039,6 @@ __device__ void bucket_emit(BucketLds<W, PER, EDGE>& L, uint32_t c, uint32_t a0,
         x1 = q[1];
       }
       const uint32_t i = L.sfinal[p];
-      if constexpr ((ANOMOD_BK_ABL & 16) != 0) {  // timing: no stores
-        if (x0.x == 0x12345678u && x1.w == 0x9ABCDEF0u) out.sf[a0 + i] = i;
-        continue;
-      }
       if (out.h) out.h[a0 + i] = ((uint64_t)x0.y << 32) | x0.x;  // (aggregate-only calls: none)
       out.sid[a0 + i] = ((uint64_t)x0.w << 32) | x0.z;
       out.pid[a0 + i] = ((uint64_t)x1.y << 32) | x1.x;
@@ -1275,49 +1062,25 @@ __device__ void bucket_emit(BucketLds<W, PER, EDGE>& L, uint32_t c, uint32_t a0,
 // position) and positions are arrival order).  The records come from `rec` by
 // position.  Writes the grouped columns of the bucket, its trace starts over
 // the bucket's own pairs (pin[a0 + ordinal], read before) and the trace count
-// dcnt[c] — or, EDGE, its edge records.
-template <int W, int PER, bool EDGE, int R, bool ATOMIC = false>
-__device__ bool bucket_body(BucketLds<W, PER, EDGE>& L, uint32_t c, uint32_t a0, uint32_t m,
+// dcnt[c].
+// (The sub-split is the stable wave multisplit: slots taken with LDS atomics
+// and every sub-bucket ranked by compares was built in r04 and removed, 64.1
+// vs 57.4 ms SN grouping at 2^27 traces; HISTORY.md.)
+template <int W, int PER, int R>
+__device__ void bucket_body(BucketLds<W, PER>& L, uint32_t c, uint32_t a0, uint32_t m,
                             uint64_t* __restrict__ pin, const GRec* __restrict__ rec, SoaOut out,
-                            EdgeOut eo, int kshift, uint32_t* __restrict__ dcnt,
-                            const uint64_t (&k)[PER], const bool (&v)[PER], const uint4 (&ra)[R],
-                            const uint4 (&rb)[R]) {
+                            int kshift, uint32_t* __restrict__ dcnt, const uint64_t (&k)[PER],
+                            const bool (&v)[PER], const uint4 (&ra)[R], const uint4 (&rb)[R]) {
   static_assert(W >= kSub, "one thread per sub-digit");
-  constexpr bool REG = R == PER;
-  const int tid = threadIdx.x, lane = tid & (kWv - 1), w = tid / kWv;
-  (void)tid;
-  (void)lane;
-  (void)w;
-  if constexpr ((ANOMOD_BK_ABL & 32) != 0 && REG) {  // timing: arrival order, every span a trace
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const uint32_t p = (uint32_t)(w * (PER * kWv) + j * kWv + lane);
-      if (v[j]) {
-        L.sfinal[p] = (uint16_t)p;
-        L.u.pre.sflag[p] = 1;
-      }
-    }
-    __syncthreads();
-  } else if constexpr (ATOMIC) {
-    if (!bucket_rank_atomic<W, PER, EDGE, R>(L, m, kshift, k, v, ra)) return false;
-  } else {
-    bucket_rank<W, PER, EDGE, R>(L, a0, m, rec, kshift, k, v, ra, rb);
-  }
-  if constexpr (EDGE) {
-    bucket_edges(L, a0, m, k, v, ra, rb, rec, eo);
-    return true;
-  }
-  bucket_emit<W, PER, EDGE, R>(L, c, a0, m, pin, rec, out, dcnt, k, v, ra, rb);
-  return true;
+  bucket_rank<W, PER, R>(L, a0, m, rec, kshift, k, v, ra, rb);
+  bucket_emit<W, PER, R>(L, c, a0, m, pin, rec, out, dcnt, k, v, ra, rb);
 }
-
-
 
 // One bucket by one workgroup: the size checks (over-size buckets listed for
 // the big kernel, or the huge walk), the pair loads and gathers, the body.
-template <int W, int PER, bool EDGE>
-__device__ void bucket_sort_one(BucketLds<W, PER, EDGE>& L, uint32_t c, uint64_t* __restrict__ pin,
-                                const GRec* __restrict__ rec, SoaOut out, EdgeOut eo,
+template <int W, int PER>
+__device__ void bucket_sort_one(BucketLds<W, PER>& L, uint32_t c, uint64_t* __restrict__ pin,
+                                const GRec* __restrict__ rec, SoaOut out,
                                 const uint32_t* __restrict__ bstart, int kshift,
                                 uint32_t* __restrict__ dcnt, bool small,
                                 uint32_t* __restrict__ over, unsigned long long* __restrict__ over_n,
@@ -1334,16 +1097,14 @@ __device__ void bucket_sort_one(BucketLds<W, PER, EDGE>& L, uint32_t c, uint64_t
       }
       return;
     }
-    // (the fused aggregation leaves such a bucket — traces of thousands of
-    // spans side by side — to the unfused path: too_big)
-    if constexpr (!EDGE && sizeof(BucketLds<W, PER, EDGE>) >= 81920 + 16 + 4 * (W / kWv))
+    if constexpr (sizeof(BucketLds<W, PER>) >= 81920 + 16 + 4 * (W / kWv))
       bucket_huge<W>(reinterpret_cast<unsigned char*>(&L), c, a0, m, pin, rec, out, dcnt, too_big);
     else if (tid == 0)
       atomicAdd(too_big, 1ull);
     return;
   }
   if (m == 0) {
-    if (tid == 0 && !EDGE) dcnt[c] = 0;
+    if (tid == 0) dcnt[c] = 0;
     return;
   }
   // REG (the small kernel): whole records held in registers from the gather
@@ -1362,124 +1123,41 @@ __device__ void bucket_sort_one(BucketLds<W, PER, EDGE>& L, uint32_t c, uint64_t
   if constexpr (REG) {
 #pragma unroll
     for (int j = 0; j < PER; ++j) {  // the gathers: issued together, after every pair load
-      if constexpr ((ANOMOD_BK_ABL & 8) != 0) {
-        ra[j] = make_uint4((uint32_t)k[j], (uint32_t)(k[j] >> 32), (uint32_t)k[j], 0u);
-        rb[j] = make_uint4((uint32_t)(k[j] >> 32), 0u, 0u, 0u);
-        continue;
-      }
       const uint4* q = reinterpret_cast<const uint4*>(rec + (uint32_t)k[j]);
       ra[j] = v[j] ? q[0] : make_uint4(0, 0, 0, 0);
       rb[j] = v[j] ? q[1] : make_uint4(0, 0, 0, 0);
     }
   }
-  if constexpr (W == kSmallW && kRankAtomic) {
-    if (!bucket_body<W, PER, EDGE, R, true>(L, c, a0, m, pin, rec, out, eo, kshift, dcnt, k, v, ra,
-                                            rb) &&
-        tid == 0) {  // a sub-bucket too long for the compare rank: the large kernel
-      const unsigned long long i = atomicAdd(over_n, 1ull);
-      if (i < over_cap) over[i] = c;
-      else atomicAdd(too_big, 1ull);
-    }
-  } else {
-    bucket_body<W, PER, EDGE, R>(L, c, a0, m, pin, rec, out, eo, kshift, dcnt, k, v, ra, rb);
-  }
+  bucket_body<W, PER, R>(L, c, a0, m, pin, rec, out, kshift, dcnt, k, v, ra, rb);
 }
 
-#ifndef ANOMOD_BK_MINW
-#define ANOMOD_BK_MINW 1  // waves per SIMD the small bucket kernel's registers must allow
-#endif
-__global__ __launch_bounds__(kSmallW, ANOMOD_BK_MINW) void bk_bucket_kernel(
+// One workgroup per bucket, in index order (nx = 1: every XCD stays inside one
+// level-A bucket, whose records the gathers then find in the Infinity Cache).
+// A persistent form that gathers the next bucket's records while it sorts
+// this one was built in r04 and removed: 93 vs 64 ms grouping at 2^27 SN
+// traces (HISTORY.md).
+__global__ __launch_bounds__(kSmallW, 1) void bk_bucket_kernel(
     uint64_t* __restrict__ pin, const GRec* __restrict__ rec, SoaOut out,
     const uint32_t* __restrict__ bstart, int kshift, uint32_t* __restrict__ dcnt,
     uint32_t* __restrict__ over, unsigned long long* __restrict__ over_n, uint32_t over_cap,
     unsigned long long* __restrict__ too_big, uint32_t nx) {
   __shared__ BucketLds<kSmallW, kSmallPer> L;
-  bucket_sort_one<kSmallW, kSmallPer, false>(L, (uint32_t)xcd_tile(blockIdx.x, gridDim.x, nx), pin,
-                                             rec, out, EdgeOut{}, bstart, kshift, dcnt, true, over,
-                                             over_n, over_cap, too_big);
+  bucket_sort_one<kSmallW, kSmallPer>(L, (uint32_t)xcd_tile(blockIdx.x, gridDim.x, nx), pin, rec,
+                                      out, bstart, kshift, dcnt, true, over, over_n, over_cap,
+                                      too_big);
 }
 
-// Persistent, pipelined form of the small bucket kernel (ANOMOD_BK_PIPE=1): the
-// workgroups take buckets b, b + G, b + 2G, ... (so the buckets in flight are
-// neighbours: every XCD inside one level-A bucket, whose records the gathers
-// then find in the Infinity Cache), and while one sorts bucket c, the records
-// of c + G are being gathered and the pairs of c + 2G loaded — the gather
-// latency hides behind the sort instead of stalling it.
-#ifndef ANOMOD_BK_PIPE_MINB
-#define ANOMOD_BK_PIPE_MINB 2  // waves per SIMD the registers must allow
-#endif
-template <bool EDGE>
-__global__ __launch_bounds__(kSmallW, ANOMOD_BK_PIPE_MINB) void bk_bucket_pipe_kernel(
-    uint64_t* __restrict__ pin, const GRec* __restrict__ rec, SoaOut out, EdgeOut eo,
-    const uint32_t* __restrict__ bstart, uint32_t nbk, int kshift, uint32_t* __restrict__ dcnt,
-    uint32_t* __restrict__ over, unsigned long long* __restrict__ over_n, uint32_t over_cap,
-    unsigned long long* __restrict__ too_big) {
-  __shared__ BucketLds<kSmallW, kSmallPer, EDGE> L;
-  constexpr int PER = kSmallPer, kCap = kSmallW * kSmallPer;
-  const int tid = threadIdx.x, lane = tid & (kWv - 1), w = tid / kWv;
-  const uint32_t G = gridDim.x;
-  struct Slot {
-    uint32_t a0, m;
-    uint64_t k[PER];
-    bool v[PER];
-  };
-  auto load = [&](Slot& s, uint32_t c) {
-    s.a0 = 0u;
-    s.m = 0u;
-    if (c < nbk) {
-      s.a0 = bstart[c];
-      s.m = bstart[c + 1] - s.a0;
-    }
-    const bool fits = s.m <= (uint32_t)kCap;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const uint32_t p = (uint32_t)(w * (PER * kWv) + j * kWv + lane);
-      s.v[j] = fits && p < s.m;
-      s.k[j] = s.v[j] ? pin[s.a0 + p] : 0ull;
-    }
-  };
-  auto gather = [&](const Slot& s, uint4 (&ra)[PER], uint4 (&rb)[PER]) {
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      const uint4* q = reinterpret_cast<const uint4*>(rec + (uint32_t)s.k[j]);
-      ra[j] = s.v[j] ? q[0] : make_uint4(0, 0, 0, 0);
-      rb[j] = s.v[j] ? q[1] : make_uint4(0, 0, 0, 0);
-    }
-  };
-  Slot cur, nxt, nx2;
-  uint4 ra[PER], rb[PER], ran[PER], rbn[PER];
-  uint32_t c = blockIdx.x;
-  load(cur, c);
-  gather(cur, ra, rb);
-  load(nxt, c + G);
-  for (; c < nbk; c += G) {
-    gather(nxt, ran, rbn);
-    load(nx2, c + 2u * G);
-    if (cur.m > (uint32_t)kCap) {  // for the big kernel (or, EDGE, the unfused path)
-      if (tid == 0) {
-        const unsigned long long i = atomicAdd(over_n, 1ull);
-        if (i < over_cap) over[i] = c;
-        else atomicAdd(too_big, 1ull);
-      }
-    } else if (cur.m == 0u) {
-      if (tid == 0 && !EDGE) dcnt[c] = 0;
-    } else {
-      bucket_body<kSmallW, PER, EDGE, PER>(L, c, cur.a0, cur.m, pin, rec, out, eo, kshift, dcnt,
-                                           cur.k, cur.v, ra, rb);
-    }
-    __syncthreads();  // the next bucket reuses the LDS
-    cur = nxt;
-    nxt = nx2;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      ra[j] = ran[j];
-      rb[j] = rbn[j];
-    }
-  }
-}
+// Edge-record output of the fused ungrouped aggregation: per span, its
+// (parent service row * S + service) edge << 33 | error << 32 | duration,
+// the parent found in the span's trace by the first-match rule.
+struct EdgeOut {
+  uint64_t* rec;  // [n], by bucket position
+  uint32_t S;
+};
 
-// The fused ungrouped aggregation without the sort (the fused path's default;
-// ANOMOD_FUSED_JOIN=0: the sorting kernels below).  A bucket holds every span
+// The fused ungrouped aggregation: no sort.  (Sorting the bucket and scanning
+// each trace for the parent, built in r04 and removed: 71.0 + 2.1 vs 52.6 +
+// 2.1 ms at 2^27 SN traces, HISTORY.md.)  A bucket holds every span
 // of its traces, so a span's parent is found by an LDS hash join on (trace,
 // span id) over the bucket: no ranking, no trace bounds.  A repeated (trace,
 // id) resolves to its earliest arrival — the smallest level-A position, since
@@ -1537,7 +1215,8 @@ __device__ __forceinline__ uint32_t slot_cas(uint32_t* tab, uint32_t s, uint32_t
 
 // One bucket [a0, a0 + m) of the level-B pairs `pin` joined in LDS; every
 // thread of the workgroup calls it.  The records come from `rec` by the pairs'
-// level-A positions.
+// level-A positions (CONTIG, ANOMOD_JOIN_RECB=1: from the bucket's own range,
+// where bk_scatter_b_rec_kernel put them).
 template <int W, int PER, bool PACK, bool T16 = true, bool CONTIG = false>
 __device__ __forceinline__ void join_bucket(unsigned char* lds, uint32_t a0, uint32_t m,
                                             const uint64_t* __restrict__ pin,
@@ -1658,11 +1337,14 @@ constexpr int join_big_per(bool pack) { return pack ? 8 : 4; }  // 8 192 / 4 096
 
 // One workgroup per bucket; a bucket over 2 048 spans is listed for the big
 // kernel (a list overflow: the unfused path).
-// MINW: waves per SIMD the registers must allow (6 = three 512-thread
-// workgroups per CU; 8 = four, 64 VGPRs with 28 B per lane spilled); T16: u16
-// table slots (PACK at 2 048 spans: 40 KiB, else 48).
-template <bool PACK, int MINW = 6, bool T16 = !PACK, bool CONTIG = false>
-__global__ __launch_bounds__(kJoinW, MINW) void bk_join_kernel(
+// kJoinMinW: waves per SIMD the registers must allow (three 512-thread
+// workgroups per CU); T16: u16 table slots.  PACK runs with u32 slots (48
+// KiB): 48.0 ms grouping at 2^27 SN traces, against 48.3 with u16 slots (40
+// KiB) at three workgroups per CU and 49.8 at four, which spills (both built
+// in r05 and removed, HISTORY.md).
+constexpr int kJoinMinW = 6;
+template <bool PACK, bool T16, bool CONTIG = false>
+__global__ __launch_bounds__(kJoinW, kJoinMinW) void bk_join_kernel(
     const uint64_t* __restrict__ pin, const GRec* __restrict__ rec, EdgeOut eo,
     const uint32_t* __restrict__ bstart, uint32_t* __restrict__ over,
     unsigned long long* __restrict__ over_n, uint32_t over_cap,
@@ -1708,32 +1390,6 @@ __global__ __launch_bounds__(kJoinBigW) void bk_join_big_kernel(
   }
 }
 
-// The fused ungrouped aggregation's bucket kernels: the same sort, then
-// edge records instead of grouped columns.
-__global__ __launch_bounds__(kSmallW) void bk_bucket_edge_kernel(
-    uint64_t* __restrict__ pin, const GRec* __restrict__ rec, EdgeOut eo,
-    const uint32_t* __restrict__ bstart, int kshift, uint32_t* __restrict__ over,
-    unsigned long long* __restrict__ over_n, uint32_t over_cap,
-    unsigned long long* __restrict__ too_big) {
-  __shared__ BucketLds<kSmallW, kSmallPer, true> L;
-  bucket_sort_one<kSmallW, kSmallPer, true>(L, blockIdx.x, pin, rec, SoaOut{}, eo, bstart, kshift,
-                                            nullptr, true, over, over_n, over_cap, too_big);
-}
-
-__global__ __launch_bounds__(kBigW) void bk_bucket_edge_big_kernel(
-    uint64_t* __restrict__ pin, const GRec* __restrict__ rec, EdgeOut eo,
-    const uint32_t* __restrict__ bstart, int kshift, const uint32_t* __restrict__ over,
-    const unsigned long long* __restrict__ over_n, uint32_t over_cap,
-    unsigned long long* __restrict__ too_big) {
-  __shared__ BucketLds<kBigW, kBigPer, true> L;
-  const uint64_t cnt = *over_n < over_cap ? *over_n : over_cap;
-  for (uint64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
-    bucket_sort_one<kBigW, kBigPer, true>(L, over[i], pin, rec, SoaOut{}, eo, bstart, kshift,
-                                          nullptr, false, nullptr, nullptr, 0, too_big);
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(kBigW) void bk_bucket_big_kernel(
     uint64_t* __restrict__ pin, const GRec* __restrict__ rec, SoaOut out,
     const uint32_t* __restrict__ bstart, int kshift, uint32_t* __restrict__ dcnt,
@@ -1742,8 +1398,8 @@ __global__ __launch_bounds__(kBigW) void bk_bucket_big_kernel(
   __shared__ BucketLds<kBigW, kBigPer> L;
   const uint64_t cnt = *over_n < over_cap ? *over_n : over_cap;
   for (uint64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
-    bucket_sort_one<kBigW, kBigPer, false>(L, over[i], pin, rec, out, EdgeOut{}, bstart, kshift,
-                                           dcnt, false, nullptr, nullptr, 0, too_big);
+    bucket_sort_one<kBigW, kBigPer>(L, over[i], pin, rec, out, bstart, kshift, dcnt, false,
+                                    nullptr, nullptr, 0, too_big);
     __syncthreads();
   }
 }
@@ -1861,9 +1517,6 @@ BucketGeom bucket_geom(uint64_t n) {
     // 30.4 + 23.8 at 10 + 10, 32.8 + 21.3 at 11 + 9; 2^25, T = 18: 9 + 9 best,
     // 16.0 vs 16.4 / 17.8 ms grouping at 8 + 10 / 7 + 11.)
     g.DA = std::max(g.T - kDMax, std::min((g.T + 1) / 2, 9));
-    // experiment knob: level A's share of the bits (the rest, <= kDMax, to level B)
-    const int da = env_int("ANOMOD_BUCKET_DA", 0);
-    if (da > 0) g.DA = std::min(std::max(da, g.T - kDMax), kDMax);
     g.DB = g.T - g.DA;
   }
   g.tilesA = n ? (n + kBTile - 1) / kBTile : 1;
@@ -1912,22 +1565,20 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
   GRec* recs = ws->aos[0];                    // level-A records (gathered by the buckets)
   SoaOut cols = ws->aos[1] ? soa_of(ws->aos[1]) : SoaOut{};  // the grouped columns
   if (!want_h) cols.h = nullptr;              // an aggregation reads no trace_hash column
-  // the fused aggregation's per-bucket hash join (ANOMOD_FUSED_JOIN=0: the
-  // sorting bucket kernels' edge form)
-  const bool join = eo && env_int("ANOMOD_FUSED_JOIN", 1) != 0;
+  const bool join = eo != nullptr;            // the fused aggregation's per-bucket hash join
   // (records through level B: the join reads them contiguously; two levels only)
   const bool recb = join && g.DB > 0 && join_records_through_b();
+  const bool debug = env_int("ANOMOD_BUCKET_DEBUG", 0) != 0;
   uint64_t* pa = ws->pairs[0];                // level-A pairs
   uint64_t* pb = ws->pairs[1];                // level-B pairs
   hipStream_t st = ctx->stream;
   ANOMOD_HIP(ctx, hipMemsetAsync(ws->misc, 0, kMiscWords * 8, st));
 
-  // XCD-contiguous tile order per scatter level (experiment knob
-  // ANOMOD_BK_XCD: bit 0 level A, bit 1 level B, bit 2 the bucket kernel —
-  // off by default there: buckets in index order keep every XCD inside one
-  // level-A bucket, whose records the gathers then find in the Infinity Cache)
-  const int xk = env_int("ANOMOD_BK_XCD", 3);
-  const uint32_t nxA = (xk & 1) ? 8u : 1u, nxB = (xk & 2) ? 8u : 1u;
+  // XCD-contiguous tile order (xcd_tile, nx = 8) in both scatter levels, index
+  // order (nx = 1) in the bucket kernel: 68.7 ms grouping at 2^27 SN traces,
+  // against 72.2 / 72.7 with it in level A / B alone, 76.1-78.5 with neither
+  // and no gain from it in the bucket kernel too
+  // (profiles/r03_group_xcd_ab_2p27.log)
   // level A (its bucket starts bsA; btile: level-B tiles per level-A bucket)
   const uint64_t nbA = (g.tilesA + kScanRows - 1) / kScanRows;
   const unsigned dgA = (unsigned)((na + 255) / 256);
@@ -1940,12 +1591,8 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
   hipLaunchKernelGGL(bk_scan_down_kernel, dim3((unsigned)nbA, dgA), dim3(256), 0, st, ws->tcnt,
                      g.tilesA, na, ws->bsum);
   hipLaunchKernelGGL(bk_scatter_a_kernel, dim3((unsigned)g.tilesA), dim3(kBThreads), 0, st, sin,
-                     recs, pa, n, g.DA, ws->tcnt, nxA);
+                     recs, pa, n, g.DA, ws->tcnt, 8u);
   ANOMOD_HIP(ctx, hipGetLastError());
-  if (ANOMOD_BK_ABL & 2) {  // timing of level A only
-    *fallback = true;
-    return ANOMOD_OK;
-  }
   uint64_t* pin;
   const uint32_t* bstart;
   uint64_t mx = 0;
@@ -1959,7 +1606,7 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
                          ws->bsA, ws->btile, na, g.DB, ws->bstart);
       ANOMOD_HIP(ctx, hipGetLastError());
       if (int rc = max_bucket(ctx, ws->bstart, 1ull << g.T, &mx)) return rc;
-      if (env_int("ANOMOD_BUCKET_DEBUG", 0))
+      if (debug)
         std::fprintf(stderr, "bucket path: DA=%d DB=%d max bucket %llu\n", g.DA, g.DB,
                      (unsigned long long)mx);
       if (mx <= (uint64_t)(kBigW * kBigPer) || g.DB == kDMax ||
@@ -1969,24 +1616,26 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
       g.T = g.DA + g.DB;
     }
     // the join resolves repeated ids by level-A position: level B need not be
-    // stable there (ANOMOD_BK_STABLE_B=1 keeps the stable scatter for A/B);
-    // ANOMOD_JOIN_RECB=1: level B moves the records too (r06 A/B)
-    if (join && recb)
+    // stable there (grouping 52.8-53.2 -> 49.5-49.6 ms, HISTORY.md;
+    // ANOMOD_BK_STABLE_B=1 keeps the stable scatter for A/B);
+    // ANOMOD_JOIN_RECB=1: level B moves the records too (r06 A/B, measured
+    // slower: 68.0 vs 48.0 ms grouping)
+    if (recb)
       hipLaunchKernelGGL(bk_scatter_b_rec_kernel, dim3((unsigned)g.tilesB), dim3(kBThreads), 0, st,
                          pa, pb, recs, ws->aos[1], g.DB, ws->tcnt, ws->bsA, ws->btile, ws->tmap,
-                         na, nxB);
+                         na, 8u);
     else if (join && !env_int("ANOMOD_BK_STABLE_B", 0))
       hipLaunchKernelGGL(bk_scatter_b_fast_kernel, dim3((unsigned)g.tilesB), dim3(kBThreads), 0, st,
-                         pa, pb, g.DB, ws->tcnt, ws->bsA, ws->btile, ws->tmap, na, nxB);
+                         pa, pb, g.DB, ws->tcnt, ws->bsA, ws->btile, ws->tmap, na, 8u);
     else
       hipLaunchKernelGGL(bk_scatter_b_kernel, dim3((unsigned)g.tilesB), dim3(kBThreads), 0, st, pa,
-                         pb, g.DB, ws->tcnt, ws->bsA, ws->btile, ws->tmap, na, nxB);
+                         pb, g.DB, ws->tcnt, ws->bsA, ws->btile, ws->tmap, na, 8u);
     pin = pb;
     bstart = ws->bstart;
   } else {
     ANOMOD_HIP(ctx, hipGetLastError());
     if (int rc = max_bucket(ctx, ws->bsA, 1ull << g.T, &mx)) return rc;
-    if (env_int("ANOMOD_BUCKET_DEBUG", 0))
+    if (debug)
       std::fprintf(stderr, "bucket path: one level, T=%d, max bucket %llu\n", g.T,
                    (unsigned long long)mx);
     if (mx > (uint64_t)(kBigW * kBigPer)) {  // the caller retries with two levels
@@ -1999,73 +1648,21 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
   ANOMOD_HIP(ctx, hipGetLastError());
   const uint64_t nbk = 1ull << g.T;
 
-  // buckets: <= 2048 spans in the small kernel, the rest listed for the
-  // large one (<= 8192 spans, or any size holding one trace); the sub-split
-  // takes the 9 pair bits below the DB bits level B took
-  const int kshift = 64 - g.DB - kSubBits;
-  // one workgroup per bucket; ANOMOD_BK_PIPE=1: the persistent pipelined
-  // bucket kernel, as many workgroups as are resident at once (measured
-  // slower: 93 vs 64 ms grouping at 2^27 SN traces, gpurun_out/r4c_pipe_f0.log)
-  const bool pipe = env_int("ANOMOD_BK_PIPE", 0) != 0;
-  auto pipe_grid = [&](const void* fn) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kSmallW, 0) != hipSuccess)
-      per_cu = 1;
-    return (unsigned)std::min<uint64_t>(nbk, (uint64_t)std::max(ctx->num_cus, 1) *
-                                                 (uint64_t)std::max(per_cu, 1));
-  };
-  if (eo) {  // the fused ungrouped aggregation: edge records, no columns, no trace_ptr
-    if (join) {
-      // PACK: the service rides in the 12 key bits every k of a bucket shares
-      // (ANOMOD_JOIN_PACK=0 forces the separate service array: tests)
-      const bool pack = g.T >= 12 && env_int("ANOMOD_JOIN_PACK", 1) != 0;
-      const unsigned big_grid = (unsigned)std::max(ctx->num_cus, 1);
-      if (pack) {
-        // ANOMOD_JOIN_W6=1: the 3-workgroups-per-CU form (no spills; A/B)
-        // u32 slots, three workgroups per CU (48 KiB): 48.0 ms grouping at
-        // 2^27 SN traces, against 48.3 with u16 slots (40 KiB) at three and
-        // 49.8 at four per CU, which spills (gpurun_out/r5b/ab_w6.log);
-        // ANOMOD_JOIN_FORM = 1 / 2 runs those two (A/B)
-        const int jv = env_int("ANOMOD_JOIN_FORM", 0);
-        auto fn = recb ? bk_join_kernel<true, 6, false, true>
-                  : jv == 2 ? bk_join_kernel<true, 8, true>
-                  : jv == 1 ? bk_join_kernel<true, 6, true> : bk_join_kernel<true, 6, false>;
-        const GRec* jrec = recb ? ws->aos[1] : recs;
-        hipLaunchKernelGGL(fn, dim3((unsigned)nbk), dim3(kJoinW), 0, st, pin,
-                           jrec, *eo, bstart, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                           ws->misc + kMiscTooBig);
-        auto fb = recb ? bk_join_big_kernel<true, true> : bk_join_big_kernel<true>;
-        hipLaunchKernelGGL(fb,
-                           dim3(big_grid), dim3(kJoinBigW), 0, st, pin,
-                           jrec, *eo, bstart, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                           ws->misc + kMiscTooBig);
-      } else {
-        const GRec* jrec = recb ? ws->aos[1] : recs;
-        auto fs = recb ? bk_join_kernel<false, 6, true, true> : bk_join_kernel<false, 6, true>;
-        auto fb = recb ? bk_join_big_kernel<false, true> : bk_join_big_kernel<false>;
-        hipLaunchKernelGGL(fs,
-                           dim3((unsigned)nbk), dim3(kJoinW), 0, st, pin,
-                           jrec, *eo, bstart, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                           ws->misc + kMiscTooBig);
-        hipLaunchKernelGGL(fb,
-                           dim3(big_grid), dim3(kJoinBigW), 0, st, pin,
-                           jrec, *eo, bstart, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                           ws->misc + kMiscTooBig);
-      }
-    } else if (pipe)
-      hipLaunchKernelGGL(bk_bucket_pipe_kernel<true>,
-                         dim3(pipe_grid(reinterpret_cast<const void*>(bk_bucket_pipe_kernel<true>))),
-                         dim3(kSmallW), 0, st, pin, recs, SoaOut{}, *eo, bstart, (uint32_t)nbk,
-                         kshift, nullptr, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                         ws->misc + kMiscTooBig);
-    else
-      hipLaunchKernelGGL(bk_bucket_edge_kernel, dim3((unsigned)nbk), dim3(kSmallW), 0, st, pin,
-                         recs, *eo, bstart, kshift, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                         ws->misc + kMiscTooBig);
-    if (!join)
-      hipLaunchKernelGGL(bk_bucket_edge_big_kernel, dim3((unsigned)std::max(ctx->num_cus, 1)),
-                         dim3(kBigW), 0, st, pin, recs, *eo, bstart, kshift, ws->over,
-                         ws->misc + kMiscBigN, (uint32_t)nbk, ws->misc + kMiscTooBig);
+  if (join) {  // the fused ungrouped aggregation: edge records, no columns, no trace_ptr
+    // one workgroup per bucket of <= 2048 spans, the rest listed for the big
+    // kernel.  PACK: the service rides in the 12 key bits every k of a bucket
+    // shares (ANOMOD_JOIN_PACK=0 forces the separate service array: tests)
+    const bool pack = g.T >= 12 && env_int("ANOMOD_JOIN_PACK", 1) != 0;
+    auto fs = recb ? (pack ? bk_join_kernel<true, false, true> : bk_join_kernel<false, true, true>)
+                   : (pack ? bk_join_kernel<true, false> : bk_join_kernel<false, true>);
+    auto fb = recb ? (pack ? bk_join_big_kernel<true, true> : bk_join_big_kernel<false, true>)
+                   : (pack ? bk_join_big_kernel<true> : bk_join_big_kernel<false>);
+    const GRec* jrec = recb ? ws->aos[1] : recs;  // recb: the records beside the level-B pairs
+    hipLaunchKernelGGL(fs, dim3((unsigned)nbk), dim3(kJoinW), 0, st, pin, jrec, *eo, bstart,
+                       ws->over, ws->misc + kMiscBigN, (uint32_t)nbk, ws->misc + kMiscTooBig);
+    hipLaunchKernelGGL(fb, dim3((unsigned)std::max(ctx->num_cus, 1)), dim3(kJoinBigW), 0, st, pin,
+                       jrec, *eo, bstart, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
+                       ws->misc + kMiscTooBig);
     ANOMOD_HIP(ctx, hipGetLastError());
     ANOMOD_HIP(ctx, hipMemcpyAsync(ws->h_misc + kMiscRead, ws->misc + kMiscRead,
                                    (kMiscWords - kMiscRead) * 8, hipMemcpyDeviceToHost, st));
@@ -2074,19 +1671,16 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
     res->passes = g.DB ? 2 : 1;
     res->bits = g.T;
     res->bucket = true;
-    res->join = join;
     return ANOMOD_OK;
   }
-  if (pipe)
-    hipLaunchKernelGGL(bk_bucket_pipe_kernel<false>,
-                       dim3(pipe_grid(reinterpret_cast<const void*>(bk_bucket_pipe_kernel<false>))),
-                       dim3(kSmallW), 0, st, pin, recs, cols, EdgeOut{}, bstart, (uint32_t)nbk,
-                       kshift, ws->dcnt, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
-                       ws->misc + kMiscTooBig);
-  else
-    hipLaunchKernelGGL(bk_bucket_kernel, dim3((unsigned)nbk), dim3(kSmallW), 0, st, pin, recs,
-                       cols, bstart, kshift, ws->dcnt, ws->over, ws->misc + kMiscBigN,
-                       (uint32_t)nbk, ws->misc + kMiscTooBig, (xk & 4) ? 8u : 1u);
+
+  // buckets: <= 2048 spans in the small kernel, the rest listed for the
+  // large one (<= 8192 spans, or any size holding one trace); the sub-split
+  // takes the 9 pair bits below the DB bits level B took
+  const int kshift = 64 - g.DB - kSubBits;
+  hipLaunchKernelGGL(bk_bucket_kernel, dim3((unsigned)nbk), dim3(kSmallW), 0, st, pin, recs, cols,
+                     bstart, kshift, ws->dcnt, ws->over, ws->misc + kMiscBigN, (uint32_t)nbk,
+                     ws->misc + kMiscTooBig, 1u);
   hipLaunchKernelGGL(bk_bucket_big_kernel, dim3((unsigned)std::max(ctx->num_cus, 1)),
                      dim3(kBigW), 0, st, pin, recs, cols, bstart, kshift, ws->dcnt, ws->over,
                      ws->misc + kMiscBigN, (uint32_t)nbk, ws->misc + kMiscTooBig);
@@ -2106,7 +1700,7 @@ int bucket_run_geom(anomod_ctx* ctx, const anomod_spans* in, BucketGeom g, Group
   ANOMOD_HIP(ctx, hipMemcpyAsync(ws->h_misc + kMiscRead, ws->misc + kMiscRead,
                                  (kMiscWords - kMiscRead) * 8, hipMemcpyDeviceToHost, st));
   ANOMOD_HIP(ctx, hipStreamSynchronize(st));
-  if (env_int("ANOMOD_BUCKET_DEBUG", 0))
+  if (debug)
     std::fprintf(stderr, "bucket path: T=%d DA=%d DB=%d max bucket %llu, %llu over 2048, %llu too big\n",
                  g.T, g.DA, g.DB, (unsigned long long)mx, ws->h_misc[kMiscBigN],
                  ws->h_misc[kMiscTooBig]);

@@ -91,7 +91,6 @@ struct GroupResult {
   int passes = 0;   // LSD: radix passes; bucket path: scatter levels
   int bits = 0;     // key bits the passes / levels sorted on
   bool bucket = false;
-  bool join = false;  // fused aggregation: the per-bucket hash join ran (else the sorting kernels)
 };
 
 // Bucket path geometry for n spans (bucket.hip).
@@ -107,9 +106,10 @@ bool join_records_through_b();
 // Runs the bucket path over `in` (ws sized by ensure_group_ws).  *fallback =
 // true when a bucket outgrew the large per-bucket kernel: the caller groups
 // with the LSD path instead (results are identical; only speed differs).
-// With erec (the fused ungrouped aggregation): no grouped columns; every
-// span's edge record (parent service row * S + service) << 33 | error << 32 |
-// duration goes to erec[grouped position] instead (*fallback also when a
+// With erec (the fused ungrouped aggregation: the per-bucket hash join): no
+// grouped columns, no trace_ptr; every span's edge record (parent service row
+// * S + service) << 33 | error << 32 | duration goes to erec[position in its
+// bucket's range] instead (the edge table is order-free; *fallback also when a
 // bucket of long traces needs the unfused path).  want_h = false: the
 // grouped trace_hash column is not written (res->cols.h = NULL; an edge
 // aggregation of the grouped view reads no trace_hash).

@@ -959,19 +959,17 @@ int anomod_edge_aggregate_ungrouped(anomod_ctx* ctx, const anomod_spans* spans,
   // turns it off): the buckets write one 8-B edge record per span instead of
   // the grouped columns, and the edge table is taken from those records — no
   // grouped columns, no trace_ptr, no walk over them.  Each bucket finds the
-  // parents by an LDS hash join (bk_bucket_join_kernel, no sort): 52.6 + 2.1
+  // parents by an LDS hash join (bk_join_kernel, no sort): 52.6 + 2.1
   // vs 57.8 + 5.7 ms unfused at 2^27 SN traces (gpurun_out/r4u_ab.log; with
-  // the sorting bucket kernel's in-trace scan, ANOMOD_FUSED_JOIN=0, it was
-  // 71.0 + 2.1).  A set whose buckets hold traces of thousands of spans side
+  // the sorting bucket kernel's in-trace scan, removed, it was 71.0 + 2.1:
+  // HISTORY.md).  A set whose buckets hold traces of thousands of spans side
   // by side takes the unfused path below.
   const char* fz = std::getenv("ANOMOD_UNGROUPED_FUSED");
   const uint64_t n = spans->n_spans;
   if (rc == ANOMOD_OK && n > 0 && !force_lsd() && !(fz && fz[0] == '0') && n_services >= 1 &&
       n_services <= 4096 && spans->max_svc < n_services && n <= 0xFFFFFFFFull - 4096) {
-    // (the sorting bucket kernels' edge form, ANOMOD_FUSED_JOIN=0, and the
-    // records-through-level-B join write the second record buffer)
-    const char* fj = std::getenv("ANOMOD_FUSED_JOIN");
-    rc = ensure_group_ws(ctx, n, join_records_through_b() || (fj && fj[0] == '0'));
+    // (only the records-through-level-B join writes the second record buffer)
+    rc = ensure_group_ws(ctx, n, join_records_through_b());
     bool fallback = true;
     if (rc == ANOMOD_OK) rc = stage_begin(ctx, kStageGroup);
     if (rc == ANOMOD_OK) {
@@ -983,7 +981,7 @@ int anomod_edge_aggregate_ungrouped(anomod_ctx* ctx, const anomod_spans* spans,
       host_record(ctx, kHostGroupWall, host_now_ms() - t0);
       if (rc == ANOMOD_OK) rc = stage_end(ctx, kStageGroup);
       if (rc == ANOMOD_OK && !fallback) {
-        ctx->group_path = g.join ? 2 : 3;  // join / fused-sort
+        ctx->group_path = 2;  // join
         ctx->group_levels = g.passes;
         ctx->group_bits = g.bits;
         return edge_aggregate_records(ctx, erec, n, n_services, &spans->hist_form, out);

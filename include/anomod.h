@@ -217,8 +217,8 @@ int anomod_spans_group(anomod_ctx* ctx, const anomod_spans* ungrouped, anomod_sp
  * *path = 1 bucket path (two stable MSD scatters over the top *bits bits of
  * mix64(trace_hash), then one workgroup per bucket), 2 the same scatters then
  * the per-bucket hash join of anomod_edge_aggregate_ungrouped (edge records,
- * no grouped columns), 3 the same scatters then the sorting bucket kernels'
- * edge records (the fused aggregation with ANOMOD_FUSED_JOIN=0), 0 LSD path (8-bit radix passes + bucket fix-up); *levels = scatter levels / radix passes run;
+ * no grouped columns), 0 LSD path (8-bit radix passes + bucket fix-up);
+ * *levels = scatter levels / radix passes run;
  * *bits = bucket bits (bucket path) or 8 * passes.  All 0 before any grouping. */
 int anomod_ctx_group_info(const anomod_ctx* ctx, int* path, int* levels, int* bits);
 /* Size the ctx's grouping workspace (grow-only, kept until the ctx is

@@ -3,7 +3,7 @@
 consecutive traces interleaved) under alternating values of one run-time
 knob, same process, same set:
 
-  AB_VAR=ANOMOD_BK_XCD AB_VALS=0,3 python scripts/time_env_ab.py [log2_traces] [reps]
+  AB_VAR=ANOMOD_BUCKET_AVG AB_VALS=1400,1024 python scripts/time_env_ab.py [log2_traces] [reps]
 """
 import json
 import os
@@ -18,8 +18,8 @@ from anomod import _lib as L  # noqa: E402
 
 lg = int(sys.argv[1]) if len(sys.argv) > 1 else 25
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-var = os.environ.get("AB_VAR", "ANOMOD_BK_XCD")
-vals = os.environ.get("AB_VALS", "0,3").split(",")
+var = os.environ.get("AB_VAR", "ANOMOD_BUCKET_AVG")
+vals = os.environ.get("AB_VALS", "1400,1024").split(",")
 with anomod.Context(0) as ctx:
     dev = ctx.generate(anomod.SynthSpec(os.environ.get("TG_TOPO", "SN"), seed=20251103,
                                         p_orphan_ppm=100), 1 << lg)

@@ -210,20 +210,16 @@ def env_knob(monkeypatch):
     return monkeypatch.setenv
 
 
-@pytest.mark.parametrize("path,avg", [("lsd", None), ("bucket", "64"), ("bucket", "1024"),
-                                      ("pipe", "1024"), ("pipe", "64")])
+@pytest.mark.parametrize("path,avg", [("lsd", None), ("bucket", "64"), ("bucket", "1024")])
 def test_group_paths_agree(ctx, env_knob, path, avg):
     """The LSD path (ANOMOD_GROUP_PATH=lsd) and the bucket path at the
     smallest / largest mean bucket size (ANOMOD_BUCKET_AVG: one or two
     scatter levels, most buckets in the small or the large per-bucket
-    kernel), also with the persistent pipelined bucket kernel
-    (ANOMOD_BK_PIPE=1), give the oracle's grouping."""
+    kernel) give the oracle's grouping."""
     if path == "lsd":
         env_knob("ANOMOD_GROUP_PATH", "lsd")
     else:
         env_knob("ANOMOD_BUCKET_AVG", avg)
-    if path == "pipe":
-        env_knob("ANOMOD_BK_PIPE", "1")
     rng = np.random.default_rng(77)
     sp = _with_trace_hashes(_random_spanset(rng, 12, 60000, 40, dup=0.02), rng)
     big = _with_trace_hashes(_random_spanset(rng, 12, 4, 1500, dup=0.02), rng)
@@ -294,19 +290,19 @@ def test_group_pair_key_collisions(ctx, env_knob, avg):
     assert ctx.group_info()["levels"] == (2 if avg else 1)
 
 
-@pytest.mark.parametrize("join", ["1", "0"])
 @pytest.mark.parametrize("S,max_len,form", [(12, 24, None), (46, 60, None), (20, 40, None),
-                                            (12, 24, "pair"), (100, 30, None)])
-def test_ungrouped_fused_equals_unfused(ctx, env_knob, monkeypatch, S, max_len, form, join):
+                                            (12, 24, "pair"), (100, 30, None)],
+                         # the cases' ids from before ("-1": the hash join), so runs compare
+                         ids=["12-24-None-1", "46-60-None-1", "20-40-None-1", "12-24-pair-1",
+                              "100-30-None-1"])
+def test_ungrouped_fused_equals_unfused(ctx, env_knob, monkeypatch, S, max_len, form):
     """anomod_edge_aggregate_ungrouped's fused path (the default: the buckets
     write one edge record per span, the table is taken from those records)
     against the unfused one (ANOMOD_UNGROUPED_FUSED=0: grouped columns, then
     the chunk walk) and the oracle: SN / TrainTicket
     widths (direct, wide, slot stats), wide latencies (a compact-form run that
-    learns the set's form), duplicate ids, orphans, interleaved arrival.  join
-    "1": the buckets' LDS hash join on (trace, id) (the fused default); "0":
-    the sorting bucket kernel's in-trace scan."""
-    env_knob("ANOMOD_FUSED_JOIN", join)
+    learns the set's form), duplicate ids, orphans, interleaved arrival.  The
+    fused path is the buckets' LDS hash join on (trace, id)."""
     if form:
         env_knob("ANOMOD_HIST_FORM", form)
     rng = np.random.default_rng(S * 3 + max_len)
@@ -317,7 +313,7 @@ def test_ungrouped_fused_equals_unfused(ctx, env_knob, monkeypatch, S, max_len, 
     dev = ctx.upload_ungrouped(flat)
     monkeypatch.setenv("ANOMOD_UNGROUPED_FUSED", "1")
     fused = ctx.edge_aggregate(dev)
-    assert ctx.group_info()["path"] == ("join" if join == "1" else "fused-sort")
+    assert ctx.group_info()["path"] == "join"
     assert_table_equal(fused, ref)
     monkeypatch.setenv("ANOMOD_UNGROUPED_FUSED", "0")
     assert_table_equal(ctx.edge_aggregate(dev), ref)
@@ -349,8 +345,8 @@ def test_ungrouped_join_shared_ids_and_big_buckets(ctx):
     whose span ids and parent ids are identical — the (trace, id) join must
     tell them apart by the trace hash, and each trace's duplicate ids resolve
     to its own first match — and three 900-span traces in one bucket (2 700
-    spans: over the join kernel's 2 048, so the sorting large kernel's edge
-    form takes it), beside ordinary random traces."""
+    spans: over the join kernel's 2 048, so the big join kernel takes it),
+    beside ordinary random traces."""
     rng = np.random.default_rng(77)
     S = 12
 
