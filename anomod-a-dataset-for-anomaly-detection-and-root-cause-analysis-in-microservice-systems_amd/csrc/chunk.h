@@ -8,14 +8,11 @@
 #include "common.h"
 
 namespace anomod {
-namespace {  // internal linkage: a kernel file may pick its own chunk size
+namespace {  // internal linkage
 namespace chunk {
 
-#ifndef ANOMOD_STAGE
-#define ANOMOD_STAGE 256
-#endif
 constexpr int kWave = 64;
-constexpr int kStage = ANOMOD_STAGE;  // spans staged per wave chunk
+constexpr int kStage = 256;  // spans staged per wave chunk
 constexpr int kPer = kStage / kWave;
 static_assert(kStage % kWave == 0 && kStage <= 1024, "chunk size");
 
@@ -37,29 +34,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, uint32_
                                            0x00020000);
 }
 
-// Cache policy of the streamed span-column loads (aux bits: 1 = sc0, 2 = nt,
-// 16 = sc1); every column is read once per launch.
-#ifndef ANOMOD_LOAD_AUX
-#define ANOMOD_LOAD_AUX 0
-#endif
-
+// Streamed span-column loads with the default cache policy (aux 0); every
+// column is read once per launch.
 __device__ __forceinline__ uint64_t bload64(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return (uint64_t)__builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, ANOMOD_LOAD_AUX);
+  return (uint64_t)__builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0);
 }
 
 __device__ __forceinline__ uint32_t bload32(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, ANOMOD_LOAD_AUX);
-}
-
-// Streamed per-span output stores (written once, never re-read by the
-// kernel): plain, or nontemporal with ANOMOD_STORE_NT.
-#ifndef ANOMOD_STORE_NT
-#define ANOMOD_STORE_NT 0
-#endif
-template <class T>
-__device__ __forceinline__ void st_out(T* p, T v) {
-  if constexpr (ANOMOD_STORE_NT) __builtin_nontemporal_store(v, p);
-  else *p = v;
+  return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0);
 }
 
 // One wave's chunk: up to 64 consecutive traces holding <= kStage spans, or a
@@ -167,29 +149,17 @@ __device__ __forceinline__ uint32_t trace_in_chunk(const uint64_t (&Sm)[kPer], i
 // a callee's spans after the calling span) or near the trace start (the
 // caller's entry span); simulated row-steps per 256-span chunk: TrainTicket
 // 18.8 -> 9.2, SocialNetwork 6.5 -> 4.0.
-#ifndef ANOMOD_FWD
-#define ANOMOD_FWD 6
-#endif
-#ifndef ANOMOD_BWD
-#define ANOMOD_BWD 4
-#endif
-constexpr uint32_t kFwd = ANOMOD_FWD, kBwd = ANOMOD_BWD;
+constexpr uint32_t kFwd = 6, kBwd = 4;
 static_assert(kFwd % 2 == 0 && kBwd % 2 == 0 && kFwd + kBwd <= 16, "bidirectional step");
 // Ids are staged with this many entries of slack past the chunk (edge_agg.hip
 // kWSid, trace_struct.hip kTSid): a forward block may read that far past the
 // trace end, so no forward block is wider.
 constexpr uint32_t kScanSlack = 16;
 
-// MAXS > 0: give up after that many steps and return -2 (not found yet; the
-// caller completes the lookup cooperatively).
-// SEL: the matches found by selects (lowest matching slot of each block, kept
-// if inside the block's valid range) with both blocks' loads issued before
-// the one branch — otherwise the compiler sinks the backward block's loads
-// under the forward block's test, two LDS round trips per step.
-template <uint32_t FW = kFwd, uint32_t BW = kBwd, int MAXS = 0, bool SEL = false>
+// The span of [a, b) whose id is pid, for span i of that trace (-1: none).
+template <uint32_t FW = kFwd, uint32_t BW = kBwd>
 __device__ __forceinline__ int find_parent_bidir(const uint64_t* lsid, uint32_t a, uint32_t b,
                                                  uint32_t i, uint64_t pid) {
-  int steps = 0;
   // FW: the staging slack; BW < 32: the mask form shifts 1u by up to BW
   static_assert(FW % 2 == 0 && BW % 2 == 0 && FW <= kScanSlack && BW < 32, "bidirectional step");
   uint32_t f = a;             // next forward block [f, f + FW)
@@ -203,42 +173,38 @@ __device__ __forceinline__ int find_parent_bidir(const uint64_t* lsid, uint32_t 
     for (uint32_t j = 0; j < FW; ++j) v[j] = lsid[f + j];
 #pragma unroll
     for (uint32_t j = 0; j < BW; ++j) w[j] = lsid[gb + j];
-    if constexpr (SEL) {
-    uint32_t qf = FW, qb = BW;
+    // The test keeps a scope of its own: the compiler lays the loop out
+    // differently without it (an exec-mask merge more per step in the edge
+    // kernels), and every timing of this scan was taken with this layout.
+    {
+      uint32_t mf = 0, mb = 0;
 #pragma unroll
-    for (int j = (int)FW - 1; j >= 0; --j) qf = v[j] == pid ? (uint32_t)j : qf;
+      for (uint32_t j = 0; j < FW; ++j) mf |= (v[j] == pid ? 1u : 0u) << j;
 #pragma unroll
-    for (int j = (int)BW - 1; j >= 0; --j) qb = w[j] == pid ? (uint32_t)j : qb;
-    const uint32_t hi = (b - f) < FW ? (b - f) : FW;  // >= 1 while f < b
-    const int32_t nb = g - (int32_t)gb + 1;
-    const bool okf = qf < hi, okb = (int32_t)qb < nb;
-    if (okf || okb) return (int)(okf ? f + qf : gb + qb);
-    } else {
-    uint32_t mf = 0, mb = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < FW; ++j) mf |= (v[j] == pid ? 1u : 0u) << j;
-#pragma unroll
-    for (uint32_t j = 0; j < BW; ++j) mb |= (w[j] == pid ? 1u : 0u) << j;
-    const uint32_t hi = (b - f) < FW ? (b - f) : FW;  // >= 1 while f < b
-    mf &= (1u << hi) - 1u;
-    // backward lanes past g (the clamp re-reads) or with g < a hold nothing new
-    const int32_t nb = g - (int32_t)gb + 1;
-    mb &= nb > 0 ? (1u << (uint32_t)nb) - 1u : 0u;
-    if (mf) return (int)(f + __ffs(mf) - 1u);
-    if (mb) return (int)(gb + 31u - __clz(mb));  // unique ids: any match is the match
+      for (uint32_t j = 0; j < BW; ++j) mb |= (w[j] == pid ? 1u : 0u) << j;
+      const uint32_t hi = (b - f) < FW ? (b - f) : FW;  // >= 1 while f < b
+      mf &= (1u << hi) - 1u;
+      // backward lanes past g (the clamp re-reads) or with g < a hold nothing new
+      const int32_t nb = g - (int32_t)gb + 1;
+      mb &= nb > 0 ? (1u << (uint32_t)nb) - 1u : 0u;
+      if (mf) return (int)(f + __ffs(mf) - 1u);
+      if (mb) return (int)(gb + 31u - __clz(mb));  // unique ids: any match is the match
     }
     f += FW;
     g -= (int32_t)BW;
     if (f >= b) return -1;
-    if (MAXS > 0 && ++steps >= MAXS) return -2;
   }
 }
 
-// find_parent_bidir<SEL> over ids staged as two u32 planes (lo[], hi[]): the
-// steps compare low words only (half the LDS bytes, 32-bit compares), and a
-// low-word candidate is confirmed on its high word; a false candidate (two ids
-// of the trace sharing a low word) finishes with an exact forward scan of the
-// trace.  Unique ids: any confirmed match is the match.
+// find_parent_bidir over ids staged as two u32 planes (lo[], hi[]): the steps
+// compare low words only (half the LDS bytes, 32-bit compares) and find the
+// matches by selects (lowest matching slot of each block, kept if inside the
+// block's valid range) with both blocks' loads issued before the one branch —
+// otherwise the compiler sinks the backward block's loads under the forward
+// block's test, two LDS round trips per step.  A low-word candidate is
+// confirmed on its high word; a false candidate (two ids of the trace sharing
+// a low word) finishes with an exact forward scan of the trace.  Unique ids:
+// any confirmed match is the match.
 template <uint32_t FW, uint32_t BW>
 __device__ __forceinline__ int find_parent_split(const uint32_t* lo, const uint32_t* hi, uint32_t a,
                                                  uint32_t b, uint32_t i, uint64_t pid) {
@@ -272,31 +238,6 @@ __device__ __forceinline__ int find_parent_split(const uint32_t* lo, const uint3
     f += FW;
     g -= (int32_t)BW;
     if (f >= b) return -1;
-  }
-}
-
-// The first span of [a_j, b_j) whose id is pid_j for each lane j of `pend`
-// (wave-uniform mask), the whole wave scanning 64 ids per step with a ballot:
-// the lookups the per-lane scans left after their first steps (a row would
-// otherwise wait for its slowest lane).  First match in trace order.
-__device__ __forceinline__ void coop_parent(const uint64_t* lsid, uint64_t pend, int lane,
-                                            uint64_t pid, uint32_t a, uint32_t b, int& q) {
-  while (pend) {
-    const int j = __ffsll((unsigned long long)pend) - 1;
-    const uint64_t pj = readlane64(pid, j);
-    const uint32_t aj = (uint32_t)__builtin_amdgcn_readlane((int)a, j);
-    const uint32_t bj = (uint32_t)__builtin_amdgcn_readlane((int)b, j);
-    int qj = -1;
-    for (uint32_t s0 = aj; s0 < bj; s0 += kWave) {
-      const uint32_t sp = s0 + (uint32_t)lane;
-      const uint64_t hit = __ballot(sp < bj && lsid[sp < bj ? sp : aj] == pj);
-      if (hit) {
-        qj = (int)(s0 + (uint32_t)__ffsll((unsigned long long)hit) - 1u);
-        break;
-      }
-    }
-    if (lane == j) q = qj;
-    pend &= pend - 1ull;
   }
 }
 

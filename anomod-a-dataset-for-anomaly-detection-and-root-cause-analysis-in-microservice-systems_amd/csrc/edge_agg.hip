@@ -48,10 +48,7 @@ namespace anomod {
 namespace {
 
 using namespace chunk;
-#ifndef ANOMOD_WAVES
-#define ANOMOD_WAVES 16
-#endif
-constexpr int kWavesPerWG = ANOMOD_WAVES;
+constexpr int kWavesPerWG = 16;
 constexpr int kThreads = kWave * kWavesPerWG;
 // LDS histogram table, two forms in the same 64 KiB (see ht_* below).
 enum HistForm { kHtHbm = 0, kHtPair = 1, kHtCompact = 2,
@@ -63,30 +60,18 @@ constexpr int kCmpBucketLog2 = 12;   // compact: 4096 buckets of 4 (key | count 
 constexpr uint32_t kCmpSlots = 4u << kCmpBucketLog2;
 constexpr int kHtBytes = 65536;
 static_assert(kPairSlots * 8 == kHtBytes && kCmpSlots * 4 == kHtBytes, "64 KiB table");
-#ifndef ANOMOD_LDS_EDGES
-#define ANOMOD_LDS_EDGES 512
-#endif
-constexpr uint32_t kLdsEdges = ANOMOD_LDS_EDGES;
+constexpr uint32_t kLdsEdges = 512;
 constexpr uint32_t kBins = ANOMOD_HIST_BINS;
 // Experiment-only ablations (never set in the shipped build): 1 = no stats,
-// 2 = no histogram, 4 = no parent lookup, 16 = stream the columns only,
-// 32 = compact histogram adds without the wrap check (non-returning), 64 =
-// compact-form spans whose two buckets are full are dropped (not counted).
+// 2 = no histogram, 4 = no parent lookup, 16 = stream the columns only.
 #ifndef ANOMOD_ABL
 #define ANOMOD_ABL 0
 #endif
-#ifndef ANOMOD_LOAD16
-#define ANOMOD_LOAD16 0
-#endif
-static_assert(!ANOMOD_LOAD16 || (ANOMOD_ABL & 16), "16-B loads: stream-only timing builds");
 
 // LDS carve (bytes, every offset a multiple of 16).
 constexpr int kOffHt = 0;                      // u32 keys (pair) | u32 slots (compact); 0 = empty
 constexpr int kOffHc = kOffHt + (int)kPairSlots * 4;  // u32 counts (pair form)
-#ifndef ANOMOD_SUM_REPS
-#define ANOMOD_SUM_REPS 8
-#endif
-constexpr uint32_t kSumReps = ANOMOD_SUM_REPS;           // u64 sum replicas per edge
+constexpr uint32_t kSumReps = 8;                         // u64 sum replicas per edge
 constexpr int kOffSum = kOffHt + kHtBytes;               // u64 [kLdsEdges][kSumReps]
 // Per-edge stats in LDS, two forms.  Direct (E <= kLdsEdges: every SN-width
 // table): (min, max) pairs and error counts indexed by edge.  Slot-hashed
@@ -103,10 +88,7 @@ constexpr int kOffErr = kOffMm + (int)kLdsEdges * 8;     // u32 error counts (di
 // Wide direct form (kLdsEdges < E <= kWideEdges, e.g. TrainTicket: E = 48 *
 // 46 = 2208): one 16-B entry {u64 sum, u32 min, u32 max} per edge + u32
 // error counts, indexed by edge (no slot hashing, no sum replicas).
-#ifndef ANOMOD_WIDE_EDGES
-#define ANOMOD_WIDE_EDGES 2304
-#endif
-constexpr uint32_t kWideEdges = ANOMOD_WIDE_EDGES;
+constexpr uint32_t kWideEdges = 2304;
 constexpr int kOffWideErr = kOffSum + (int)kWideEdges * 16;
 constexpr int kStatsEnd = std::max({kOffMm + (int)(kLdsEdges * 12),   // direct
                                     kOffMm + (int)(kSlotEdges * 16),  // slot
@@ -383,10 +365,10 @@ __device__ __forceinline__ void record(unsigned char* smem, uint32_t edge, uint3
                       (y.y == 0u) | (y.z == 0u) | (y.w == 0u);
     stat_add<ST>(smem, edge, d, fl, tab, pk);
     if (hit) {
-      if (!(ANOMOD_ABL & 32)) ht_wrap(old, key, tab.kb, tab.hist);
+      ht_wrap(old, key, tab.kb, tab.hist);
     } else if (room) {
       ht_insert_cmp(hk, key, s0, s1, tab.kb, tab.hist);
-    } else if (!(ANOMOD_ABL & 64)) {
+    } else {
       atomicAdd(&tab.hist[key - 1u], 1ull);
     }
   }
@@ -400,33 +382,11 @@ struct Regs {
 };
 
 __device__ __forceinline__ void load_regs(const Cols& col, const Chunk& c, int lane, Regs& R) {
-  const uint32_t n = c.k ? c.n : 0u;  // a big trace is read by edge_big_kernel
+  const uint32_t n = c.k ? c.n : 0u;  // a long trace is read by the long-trace pass
   const auto rsid = rsrc(col.span_id + c.base, n * 8u);
   const auto rpid = rsrc(col.parent + c.base, n * 8u);
   const auto rsf = rsrc(col.svcfl + c.base, n * 4u);
   const auto rdur = rsrc(col.dur + c.base, n * 4u);
-#if ANOMOD_LOAD16  // timing experiment (stream-only builds): 16 B per lane and load
-  static_assert(kPer == 4, "16-B loads: 4 rows");
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const uint32_t i = (uint32_t)(j * 128 + 2 * lane);
-    const auto a = __builtin_amdgcn_raw_buffer_load_b128(rsid, (int)(i * 8u), 0, ANOMOD_LOAD_AUX);
-    const auto b = __builtin_amdgcn_raw_buffer_load_b128(rpid, (int)(i * 8u), 0, ANOMOD_LOAD_AUX);
-    R.sid[2 * j] = ((uint64_t)a[1] << 32) | a[0];
-    R.sid[2 * j + 1] = ((uint64_t)a[3] << 32) | a[2];
-    R.pid[2 * j] = ((uint64_t)b[1] << 32) | b[0];
-    R.pid[2 * j + 1] = ((uint64_t)b[3] << 32) | b[2];
-  }
-  {
-    const auto c = __builtin_amdgcn_raw_buffer_load_b128(rsf, (int)(lane * 16u), 0, ANOMOD_LOAD_AUX);
-    const auto d = __builtin_amdgcn_raw_buffer_load_b128(rdur, (int)(lane * 16u), 0, ANOMOD_LOAD_AUX);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      R.sf[r] = c[r];
-      R.dur[r] = d[r];
-    }
-  }
-#else
 #pragma unroll
   for (int r = 0; r < kPer; ++r) {
     const uint32_t i = (uint32_t)lane + (uint32_t)(r * kWave);
@@ -435,31 +395,18 @@ __device__ __forceinline__ void load_regs(const Cols& col, const Chunk& c, int l
     R.sf[r] = bload32(rsf, i * 4u);
     R.dur[r] = bload32(rdur, i * 4u);
   }
-#endif
 }
 
 // First span of [a, b) whose id equals pid: kScan ids per step (ds_read2_b64
 // from the trace start itself), matches folded into a bit mask.  First match
 // in trace order (the reference rule: jaeger_to_csv.py:34-38 /
 // trace_collector.py:424-443).
-#ifndef ANOMOD_SCAN_IDS
-#define ANOMOD_SCAN_IDS 10
-#endif
-constexpr uint32_t kScan = ANOMOD_SCAN_IDS;  // ids compared per step (kScan / 2 x ds_read2_b64)
-// Per-lane scan steps before a row's remaining lookups go to the whole wave
-// (coop_parent); 0 = every lane scans to the end.
-#ifndef ANOMOD_COOP_STEPS
-#define ANOMOD_COOP_STEPS 0
-#endif
-constexpr int kCoopSteps = ANOMOD_COOP_STEPS;
+constexpr uint32_t kScan = 10;  // ids compared per step (kScan / 2 x ds_read2_b64)
 static_assert(kScan % 2 == 0 && kScan <= 16, "scan step");
 
-template <int MAXS = 0>  // > 0: -2 after that many steps (completed cooperatively)
 __device__ __forceinline__ int find_parent(const uint64_t* lsid, uint32_t a, uint32_t b,
                                            uint64_t pid) {
-  int steps = 0;
   for (uint32_t q0 = a; q0 < b; q0 += kScan) {
-    if (MAXS > 0 && steps++ >= MAXS) return -2;
     uint64_t v[kScan];
 #pragma unroll
     for (uint32_t j = 0; j < kScan; ++j) v[j] = lsid[q0 + j];
@@ -475,49 +422,19 @@ __device__ __forceinline__ int find_parent(const uint64_t* lsid, uint32_t a, uin
 
 // Scan widths of the bidirectional parent scan: (kFwd, kBwd) = (6, 4) for
 // collector-ordered traces of tens of spans (SN / TrainTicket: 8 / 8 measured
-// 2-10 % slower there), (8, 8) for sets holding traces longer than a chunk
-// (LONG: random ancestors in 128- and 256-span traces, 7.52 vs 8.09 ms).
-// r05: the TrainTicket-width and long-trace instantiations take the
-// select-built scan (one LDS round trip per step): TT 2^27 17.8-18.4 vs
-// 18.5-18.7 ms, LONG 2^23 7.24-7.29 vs 7.60-7.69; the SN pair form gains
-// nothing measurable and keeps the mask form (profiles/r05_experiments/
-// parent_scan_sel_widths.log).  Then both take the split-word form
-// (chunk.h find_parent_split: ids staged as u32 planes, low words compared,
-// the candidate confirmed on its high word), whose cheaper steps pay for
-// wider ones: TT 12 / 4 16.3-16.7 ms, LONG 12 / 4 6.96-7.04
-// (split_scan_*.log); the SN pair form again gains nothing.
-#ifndef ANOMOD_SEL_SN
-#define ANOMOD_SEL_SN 0
-#endif
-#ifndef ANOMOD_SEL_WIDE
-#define ANOMOD_SEL_WIDE 1
-#endif
-#ifndef ANOMOD_SEL_LONG
-#define ANOMOD_SEL_LONG 1
-#endif
-#ifndef ANOMOD_SPLIT_LONG
-#define ANOMOD_SPLIT_LONG 1
-#endif
-#ifndef ANOMOD_SPLIT_WIDE
-#define ANOMOD_SPLIT_WIDE 1
-#endif
-#ifndef ANOMOD_SPLIT_SN
-#define ANOMOD_SPLIT_SN 0
-#endif
-#ifndef ANOMOD_LFWD
-#define ANOMOD_LFWD 12
-#endif
-#ifndef ANOMOD_LBWD
-#define ANOMOD_LBWD 4
-#endif
-constexpr uint32_t kLFwd = ANOMOD_LFWD, kLBwd = ANOMOD_LBWD;  // the long-trace sets' widths
-#ifndef ANOMOD_WFWD
-#define ANOMOD_WFWD 12
-#endif
-#ifndef ANOMOD_WBWD
-#define ANOMOD_WBWD 4
-#endif
-constexpr uint32_t kWFwd = ANOMOD_WFWD, kWBwd = ANOMOD_WBWD;  // TrainTicket width, split scan
+// 2-10 % slower there); sets holding traces longer than a chunk first took
+// (8, 8) (LONG: random ancestors in 128- and 256-span traces, 7.52 vs 8.09
+// ms).  The TrainTicket-width and long-trace instantiations then gained from
+// building the matches with selects (one LDS round trip per step): TT 2^27
+// 17.8-18.4 vs 18.5-18.7 ms, LONG 2^23 7.24-7.29 vs 7.60-7.69
+// (profiles/r05_experiments/parent_scan_sel_widths.log), and again from the
+// split-word form (chunk.h find_parent_split: ids staged as u32 planes, low
+// words compared, the candidate confirmed on its high word), whose cheaper
+// steps pay for wider ones: TT 12 / 4 16.3-16.7 ms, LONG 12 / 4 6.96-7.04
+// (split_scan_*.log).  The SN pair form gained nothing measurable from either
+// and keeps the mask form over u64 ids at (kFwd, kBwd).
+constexpr uint32_t kLFwd = 12, kLBwd = 4;  // the long-trace sets' widths
+constexpr uint32_t kWFwd = 12, kWBwd = 4;  // TrainTicket width, split scan
 template <int HT, int ST, bool UNI, bool WIDE = false>
 __device__ __forceinline__ void process_chunk(unsigned char* smem, unsigned char* wsm, int lane,
                                               const Chunk& c, const Regs& R, uint32_t S,
@@ -525,15 +442,11 @@ __device__ __forceinline__ void process_chunk(unsigned char* smem, unsigned char
   auto* lsid = reinterpret_cast<uint64_t*>(wsm + kWSid);
   auto* lsvc = reinterpret_cast<uint16_t*>(wsm + kWSvc);
   auto* lflag = reinterpret_cast<uint8_t*>(wsm + kWFlag);
-  // select-built scan (chunk.h find_parent_bidir SEL) per table form
-  constexpr bool kSel = WIDE ? ANOMOD_SEL_LONG != 0
-                             : (ST == kStWide ? ANOMOD_SEL_WIDE != 0 : ANOMOD_SEL_SN != 0);
-  // TrainTicket-width and long-trace sets with unique ids: ids staged as u32
-  // planes, low words scanned (chunk.h find_parent_split; it takes precedence
-  // over kSel)
-  constexpr bool kSplit =
-      UNI && kCoopSteps == 0 &&
-      (WIDE ? ANOMOD_SPLIT_LONG != 0 : (ST == kStWide ? ANOMOD_SPLIT_WIDE != 0 : ANOMOD_SPLIT_SN != 0));
+  // Unique-id sets in the TrainTicket-width and long-trace instantiations
+  // stage ids as two u32 planes and scan low words (find_parent_split);
+  // everything else stages u64 ids: unique-id sets then scan from both ends
+  // (find_parent_bidir), other sets forward for the first match (find_parent).
+  constexpr bool kSplit = UNI && (WIDE || ST == kStWide);
   auto* llo = reinterpret_cast<uint32_t*>(wsm + kWSid);
   uint32_t* lhi = llo + (kStage + chunk::kScanSlack);
   if constexpr (ANOMOD_ABL & 16) {  // stream only: keep the loads, do nothing
@@ -562,21 +475,7 @@ __device__ __forceinline__ void process_chunk(unsigned char* smem, unsigned char
   for (int r = 0; r < kPer; ++r) {
     const uint32_t i = lane + r * kWave;
     uint32_t p = S;  // ROOT
-    if constexpr (kCoopSteps > 0 && !(ANOMOD_ABL & 4)) {
-      // kCoopSteps scan steps per lane, then the row's remaining lookups by
-      // the whole wave (coop_parent)
-      const bool has = i < c.n && R.pid[r] != 0ull;
-      uint32_t a, b;
-      trace_bounds(Sm, r, lane, c.n, a, b);
-      int q = -1;
-      if (has) {
-        q = UNI ? (WIDE ? find_parent_bidir<kLFwd, kLBwd, kCoopSteps, kSel>(lsid, a, b, i, R.pid[r])
-                        : find_parent_bidir<kFwd, kBwd, kCoopSteps, kSel>(lsid, a, b, i, R.pid[r]))
-                : find_parent<kCoopSteps>(lsid, a, b, R.pid[r]);
-      }
-      coop_parent(lsid, __ballot(q == -2), lane, R.pid[r], a, b, q);
-      if (has) p = q >= 0 ? lsvc[q] : S + 1u;  // ORPHAN unless found in the trace
-    } else if (i < c.n && R.pid[r] != 0ull) {
+    if (i < c.n && R.pid[r] != 0ull) {
       p = S + 1u;  // ORPHAN unless found in the trace
       if constexpr (!(ANOMOD_ABL & 4)) {
         uint32_t a, b;
@@ -584,13 +483,10 @@ __device__ __forceinline__ void process_chunk(unsigned char* smem, unsigned char
         int q;
         if constexpr (kSplit && WIDE)
           q = find_parent_split<kLFwd, kLBwd>(llo, lhi, a, b, i, R.pid[r]);
-        else if constexpr (kSplit && ST == kStWide)
-          q = find_parent_split<kWFwd, kWBwd>(llo, lhi, a, b, i, R.pid[r]);
         else if constexpr (kSplit)
-          q = find_parent_split<kFwd, kBwd>(llo, lhi, a, b, i, R.pid[r]);
+          q = find_parent_split<kWFwd, kWBwd>(llo, lhi, a, b, i, R.pid[r]);
         else
-          q = UNI ? (WIDE ? find_parent_bidir<kLFwd, kLBwd, 0, kSel>(lsid, a, b, i, R.pid[r])
-                          : find_parent_bidir<kFwd, kBwd, 0, kSel>(lsid, a, b, i, R.pid[r]))
+          q = UNI ? find_parent_bidir<kFwd, kBwd>(lsid, a, b, i, R.pid[r])
                   : find_parent(lsid, a, b, R.pid[r]);
         if (q >= 0) p = lsvc[q];
       } else {  // ablation: a parent-like edge without the lookup (keeps key diversity)
@@ -731,343 +627,43 @@ __device__ __forceinline__ void tables_flush(unsigned char* smem, uint32_t E, co
   }
 }
 
-// Traces longer than kStage do not fit a wave's staging area: the chunk walk
-// only lists them (big_list[j] = trace index, big[0] = count), and
-// edge_big_kernel resolves them afterwards, one workgroup per trace.  Its LDS
-// holds the same private histogram / per-edge stats tables as the chunk walk
-// (flushed once at the end) and, in the wave-staging area's place, a hash
-// table of kBigWin span ids at a time (id -> first position in the window,
-// atomicMin); the trace's spans are looked up kBigPer per thread against the
+// ---- long-trace pass: resolve, then record ---------------------------------
+// Traces longer than kBigMin (<= kStage) do not go through a wave's staging
+// area: the chunk walk only lists them (big_list[j] = trace index, big[0] =
+// count), and two kernels handle them afterwards.
+//
+// edge_big_resolve_kernel holds a hash table of kResWin span ids at a time
+// (id -> first position in the window, atomicMin, with that span's service)
+// and nothing else (48 KiB: three 512-thread workgroups per CU).  A trace
+// longer than a window is looked up kBigPer spans per thread against its
 // windows in trace order, so the first window holding a span's parent
-// reference gives the first match (the reference rule).
-// O(L * ceil(L / kBigWin)) work, O(L) for L <= kBigWin.
-constexpr int kBigThreads = kThreads;  // the tables' init / flush loops assume it
-#ifndef ANOMOD_BIG_MIN
-#define ANOMOD_BIG_MIN 256
-#endif
-// resolve kernel: minimum waves per SIMD the compiler must fit (registers)
-#ifndef ANOMOD_RES_MINB
-#define ANOMOD_RES_MINB 2
-#endif
-// 1 = the r02 single-kernel long-trace pass (experiment builds, A/B)
-#ifndef ANOMOD_BIG_ONEPASS
-#define ANOMOD_BIG_ONEPASS 0
-#endif
-// traces longer than this take the long-trace pass (<= kStage)
-constexpr uint32_t kBigMin = ANOMOD_BIG_MIN;
-constexpr uint32_t kBigWin = 2048;    // ids per table window
-constexpr uint32_t kBigSlots = 4096;  // table slots (load <= 0.5)
-#ifndef ANOMOD_BIG_PER
-#define ANOMOD_BIG_PER 8
-#endif
-constexpr int kBigPer = ANOMOD_BIG_PER;  // spans per thread per lookup block
-constexpr int kOffBigKey = kOffWave;                          // u64 [kBigSlots], 0 = empty
-constexpr int kOffBigPos = kOffBigKey + (int)kBigSlots * 8;   // u32 [kBigSlots]
-static_assert(kBigWin % kBigThreads == 0 && kBigWin <= 65536, "window: whole rows, position << 16 | svc");
-constexpr int kBigLdsBytes = kOffBigPos + (int)kBigSlots * 4;
-static_assert(kBigLdsBytes <= 160 * 1024, "long-trace pass LDS budget");
-
-__device__ __forceinline__ uint32_t big_slot(uint64_t id) {
-  return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> (64 - 12)) & (kBigSlots - 1u);
-}
-
-// One trace longer than kBigWin spans: blocks of kBigThreads * kBigPer
-// spans, each looked up against the trace's id windows in order (the first
-// window holding a parent reference gives its first match).
-template <int HT, int ST>
-__device__ void big_one(unsigned char* smem, const uint64_t* __restrict__ span_id,
-                        const uint64_t* __restrict__ parent, const uint32_t* __restrict__ svcfl,
-                        const uint32_t* __restrict__ dur, uint64_t lo, uint64_t L, uint32_t S,
-                        const Table& tab) {
-  auto* bkey = reinterpret_cast<unsigned long long*>(smem + kOffBigKey);
-  auto* bval = reinterpret_cast<uint32_t*>(smem + kOffBigPos);
-  const int tid = threadIdx.x;
-  for (uint64_t b0 = 0; b0 < L; b0 += (uint64_t)kBigThreads * kBigPer) {
-    uint64_t pid[kBigPer];
-    uint32_t sf[kBigPer], dr[kBigPer], psv[kBigPer];  // psv: parent's service (~0: none yet)
-    bool need = false;
-#pragma unroll
-    for (int r = 0; r < kBigPer; ++r) {
-      const uint64_t i = b0 + (uint64_t)r * kBigThreads + tid;
-      pid[r] = i < L ? parent[lo + i] : 0ull;
-      sf[r] = i < L ? svcfl[lo + i] : 0u;
-      dr[r] = i < L ? dur[lo + i] : 0u;
-      psv[r] = 0xFFFFFFFFu;
-      need |= pid[r] != 0ull;
-    }
-    for (uint64_t w0 = 0; w0 < L; w0 += kBigWin) {
-      if (!__syncthreads_or(need)) break;  // also orders the previous clear
-      constexpr int kIns = kBigWin / kBigThreads;
-      uint64_t id[kIns];
-      uint32_t sv[kIns];
-#pragma unroll
-      for (int u = 0; u < kIns; ++u) {
-        const uint32_t k = (uint32_t)(u * kBigThreads + tid);
-        id[u] = w0 + k < L ? span_id[lo + w0 + k] : 0ull;
-        sv[u] = w0 + k < L ? svcfl[lo + w0 + k] & 0xFFFFu : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < kIns; ++u) {
-        if (id[u] == 0ull) continue;
-        const uint32_t k = (uint32_t)(u * kBigThreads + tid);
-        for (uint32_t sl = big_slot(id[u]);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-          const unsigned long long prev = atomicCAS(&bkey[sl], 0ull, (unsigned long long)id[u]);
-          if (prev == 0ull || prev == id[u]) {
-            atomicMin(&bval[sl], (k << 16) | sv[u]);  // the first position wins, with its service
-            break;
-          }
-        }
-      }
-      __syncthreads();
-      need = false;
-#pragma unroll
-      for (int r = 0; r < kBigPer; ++r) {
-        if (pid[r] == 0ull || psv[r] != 0xFFFFFFFFu) continue;
-        for (uint32_t sl = big_slot(pid[r]);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-          const unsigned long long key = bkey[sl];
-          if (key == pid[r]) {
-            psv[r] = bval[sl] & 0xFFFFu;
-            break;
-          }
-          if (key == 0ull) break;
-        }
-        need |= psv[r] == 0xFFFFFFFFu;
-      }
-      __syncthreads();
-      for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-        bkey[k] = 0ull;
-        bval[k] = 0xFFFFFFFFu;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kBigPer; ++r) {
-      const uint64_t i = b0 + (uint64_t)r * kBigThreads + tid;
-      if (i >= L) continue;
-      const uint32_t p = pid[r] == 0ull ? S : psv[r] == 0xFFFFFFFFu ? S + 1u : psv[r];
-      const uint32_t edge = p * S + (sf[r] & 0xFFFFu);
-      if constexpr (HT == kHtKeys) {
-        tab.keys[lo + i] = ((unsigned long long)edge << 32) | dr[r];
-      } else {
-        record<HT, ST>(smem, edge, dr[r], sf[r] >> 16, tab);
-      }
-    }
-  }
-  __syncthreads();  // the last window's clear before the next user of the table
-}
-
-// Up to kGroup listed traces of <= kBigWin spans packed into ONE table window
-// (r03): trace i owns table slots [2 off_i, 2 off_i + 2 L_i) (load 1/2;
-// range reduction by multiply-shift, linear probing inside the region), so
-// ids of different traces never meet, and a workgroup pays the
+// reference gives the first match (the reference rule): O(L * ceil(L /
+// kResWin)) work, O(L) for L <= kResWin.  Shorter traces are packed, up to
+// kGroup of them, into ONE window: trace i owns table slots [2 off_i, 2 off_i
+// + 2 L_i) (load 1/2; range reduction by multiply-shift, linear probing inside
+// the region), so ids of different traces never meet, and a workgroup pays the
 // load / insert / lookup round trips once per batch instead of once per
-// trace.  <= 2 spans per thread (sum L_i <= kBigWin = 2 x kBigThreads).
-#ifndef ANOMOD_BIG_GROUP
-#define ANOMOD_BIG_GROUP 4
-#endif
-constexpr int kGroup = ANOMOD_BIG_GROUP;  // traces per ticket (one atomic, their entries and bounds loaded together)
-static_assert(kBigWin == 2 * kBigThreads, "a packed batch is two spans per thread");
-
-__device__ __forceinline__ uint32_t big_region_slot(uint64_t id, uint32_t size) {
-  return __umulhi((uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32), size);
-}
-
-// bm: the group entries (bits) packed into this window, consecutive
-template <int HT, int ST>
-__device__ void big_batch(unsigned char* smem, const uint64_t* __restrict__ span_id,
-                          const uint64_t* __restrict__ parent, const uint32_t* __restrict__ svcfl,
-                          const uint32_t* __restrict__ dur, const uint64_t (&lo)[kGroup],
-                          const uint64_t (&L)[kGroup], uint32_t bm, uint32_t S, const Table& tab) {
-  auto* bkey = reinterpret_cast<unsigned long long*>(smem + kOffBigKey);
-  auto* bval = reinterpret_cast<uint32_t*>(smem + kOffBigPos);
-  const int tid = threadIdx.x;
-  uint32_t off[kGroup + 1];  // non-members have length 0
-  off[0] = 0;
-#pragma unroll
-  for (int i = 0; i < kGroup; ++i) off[i + 1] = off[i] + (((bm >> i) & 1u) ? (uint32_t)L[i] : 0u);
-  const uint32_t tot = off[kGroup];
-  uint64_t id[2], pid[2], g[2];
-  uint32_t sf[2], dr[2], rb[2], rs[2], pos[2], psv[2];
-  bool v[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const uint32_t q = (uint32_t)(u * kBigThreads + tid);
-    v[u] = q < tot;
-    // the member holding batch position q: the last entry whose start <= q
-    // (entries before the batch start at 0 with length 0, entries after it
-    // at tot)
-    uint32_t a0 = 0, a1 = off[1];
-    uint64_t tl = lo[0];
-#pragma unroll
-    for (int i = 1; i < kGroup; ++i)
-      if (q >= off[i] && ((bm >> i) & 1u)) {
-        a0 = off[i];
-        a1 = off[i + 1];
-        tl = lo[i];
-      }
-    pos[u] = q - a0;
-    rb[u] = 2u * a0;  // the trace's table region
-    rs[u] = 2u * (a1 - a0);
-    g[u] = tl + pos[u];
-    id[u] = v[u] ? span_id[g[u]] : 0ull;
-    pid[u] = v[u] ? parent[g[u]] : 0ull;
-    sf[u] = v[u] ? svcfl[g[u]] : 0u;
-    dr[u] = v[u] ? dur[g[u]] : 0u;
-    psv[u] = 0xFFFFFFFFu;
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (!v[u] || id[u] == 0ull) continue;
-    uint32_t r = big_region_slot(id[u], rs[u]);
-    while (true) {
-      const uint32_t sl = rb[u] + r;
-      const unsigned long long prev = atomicCAS(&bkey[sl], 0ull, (unsigned long long)id[u]);
-      if (prev == 0ull || prev == id[u]) {
-        atomicMin(&bval[sl], (pos[u] << 16) | (sf[u] & 0xFFFFu));  // the first position wins
-        break;
-      }
-      r = r + 1u == rs[u] ? 0u : r + 1u;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (!v[u] || pid[u] == 0ull) continue;
-    uint32_t r = big_region_slot(pid[u], rs[u]);
-    for (uint32_t probe = 0; probe < rs[u]; ++probe) {
-      const unsigned long long key = bkey[rb[u] + r];
-      if (key == pid[u]) {
-        psv[u] = bval[rb[u] + r] & 0xFFFFu;
-        break;
-      }
-      if (key == 0ull) break;
-      r = r + 1u == rs[u] ? 0u : r + 1u;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (!v[u]) continue;
-    const uint32_t p = pid[u] == 0ull ? S : psv[u] == 0xFFFFFFFFu ? S + 1u : psv[u];
-    const uint32_t edge = p * S + (sf[u] & 0xFFFFu);
-    if constexpr (HT == kHtKeys) {
-      tab.keys[g[u]] = ((unsigned long long)edge << 32) | dr[u];
-    } else {
-      record<HT, ST>(smem, edge, dr[u], sf[u] >> 16, tab);
-    }
-  }
-  __syncthreads();  // every lookup done before the clear
-  for (uint32_t k = tid; k < 2u * tot; k += kBigThreads) {
-    bkey[k] = 0ull;
-    bval[k] = 0xFFFFFFFFu;
-  }
-  __syncthreads();
-}
-
-template <int HT, int ST>
-__global__ __launch_bounds__(kBigThreads) void edge_big_kernel(
-    const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
-    const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
-    const uint64_t* __restrict__ trace_ptr, uint32_t S, uint32_t E, Table tab) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[kBigLdsBytes];
-  __shared__ unsigned long long s_g[kGroup][2];  // the current group: first span, length (0: none)
-  auto* bkey = reinterpret_cast<unsigned long long*>(smem + kOffBigKey);  // 0 = empty (id 0 is never a parent ref)
-  auto* bval = reinterpret_cast<uint32_t*>(smem + kOffBigPos);  // (first position) << 16 | svc
-  const int tid = threadIdx.x;
-  const uint64_t nbig = tab.big[0];
-  if (nbig == 0) return;
-  tables_init<HT, ST>(smem, E, tid);
-  for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-    bkey[k] = 0ull;
-    bval[k] = 0xFFFFFFFFu;
-  }
-  // Wave 0 keeps the NEXT group of kGroup traces in flight (one ticket, the
-  // list entries and bounds loaded by lanes 0..kGroup-1 together) while the
-  // workgroup works on the current one.
-  unsigned long long nlo = 0, nL = 0;
-  auto fetch = [&]() {
-    unsigned long long j = 0;
-    if (tid == 0) j = atomicAdd(&tab.big[1], (unsigned long long)kGroup);
-    j = __shfl(j, 0);
-    nlo = nL = 0;
-    if (tid < kGroup && j + tid < nbig) {
-      const uint64_t t = tab.big_list[j + tid];
-      nlo = trace_ptr[t];
-      nL = trace_ptr[t + 1] - nlo;
-    }
-  };
-  if (tid < kWave) fetch();
-  while (true) {
-    __syncthreads();  // the previous group is done with s_g
-    if (tid < kGroup) {
-      s_g[tid][0] = nlo;
-      s_g[tid][1] = nL;
-    }
-    __syncthreads();
-    uint64_t glo[kGroup], gL[kGroup];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < kGroup; ++k) {
-      glo[k] = s_g[k][0];
-      gL[k] = s_g[k][1];
-      any |= gL[k] != 0;
-    }
-    if (!any) break;  // tickets exhausted (listed traces are never empty)
-    if (tid < kWave) fetch();  // next group, overlapping this one's work
-    // greedy in order: a trace longer than a window alone, else as many
-    // consecutive ones as one window holds (group entries addressed by
-    // compile-time indices only: the arrays stay in registers)
-    uint32_t left = 0;
-#pragma unroll
-    for (int q = 0; q < kGroup; ++q) left |= (gL[q] != 0 ? 1u : 0u) << q;
-    while (left) {
-      const int k = __ffs(left) - 1;
-      uint64_t lk = 0, Lk = 0;
-#pragma unroll
-      for (int q = 0; q < kGroup; ++q)
-        if (q == k) {
-          lk = glo[q];
-          Lk = gL[q];
-        }
-      if (Lk > kBigWin) {
-        big_one<HT, ST>(smem, span_id, parent, svcfl, dur, lk, Lk, S, tab);
-        left &= ~(1u << k);
-        continue;
-      }
-      uint32_t bm = 0;
-      uint64_t tot = 0;
-#pragma unroll
-      for (int q = 0; q < kGroup; ++q) {
-        const bool chain = q == k || (q > 0 && ((bm >> (q - 1)) & 1u));
-        if (q >= k && chain && ((left >> q) & 1u) && gL[q] <= kBigWin && tot + gL[q] <= kBigWin) {
-          bm |= 1u << q;
-          tot += gL[q];
-        }
-      }
-      big_batch<HT, ST>(smem, span_id, parent, svcfl, dur, glo, gL, bm, S, tab);
-      left &= ~bm;
-    }
-  }
-  __syncthreads();
-  tables_flush<HT, ST>(smem, E, tab, tid);
-}
-
-// ---- long-trace pass, r03: resolve, then record ----------------------------
-// The pass above holds the histogram / stats tables AND the id table in one
-// workgroup's LDS, so a CU runs one workgroup and every batch's column loads,
+// trace.  It writes every listed span's parent row — or, in the exact-quantile
+// mode, its key.
+//
+// edge_big_record_kernel streams the listed spans (16 traces per ticket, one
+// load round trip per ticket) into the same private histogram / per-edge
+// stats tables as the chunk walk, flushed once at the end.  Same first-match
+// rule, same table forms.
+//
+// Why two kernels: with the histogram / stats tables AND the id table in one
+// workgroup's LDS a CU runs one workgroup, and every batch's column loads,
 // inserts, lookups and records follow each other with nothing to hide their
-// latency (LONG at 2^23 traces: 3.74 ms for 1.3e8 listed spans).  Split:
-// edge_big_resolve_kernel keeps only the id table (48 KiB: three 512-thread
-// workgroups per CU) and writes every listed span's parent row — or, in the
-// exact-quantile mode, its key — and edge_big_record_kernel streams the
-// listed spans (16 traces per ticket, one load round trip per ticket) into
-// the chunk walk's tables.  Same first-match rule, same table forms.
-#ifndef ANOMOD_RES_THREADS
-#define ANOMOD_RES_THREADS 512
-#endif
-constexpr int kResThreads = ANOMOD_RES_THREADS;
-#ifndef ANOMOD_RES_WIN
-#define ANOMOD_RES_WIN 2048
-#endif
-constexpr uint32_t kResWin = ANOMOD_RES_WIN;       // ids per table window
+// latency (LONG at 2^23 traces: 3.74 ms for 1.3e8 listed spans).
+constexpr int kBigThreads = kThreads;  // record kernel: the tables' init / flush loops assume it
+// traces longer than this take the long-trace pass (<= kStage)
+constexpr uint32_t kBigMin = 256;
+constexpr int kBigPer = 8;  // spans per thread per lookup block
+constexpr int kGroup = 4;   // traces per ticket (one atomic, their entries and bounds loaded together)
+constexpr int kResThreads = 512;
+// minimum waves per SIMD the compiler must fit the resolve kernel in (registers)
+constexpr int kResMinWaves = 2;
+constexpr uint32_t kResWin = 2048;                 // ids per table window
 constexpr uint32_t kResSlots = 2 * kResWin;        // load <= 1/2
 static_assert((kResSlots & (kResSlots - 1)) == 0, "power-of-two table");
 __device__ __forceinline__ uint32_t res_slot(uint64_t id) {
@@ -1075,6 +671,11 @@ __device__ __forceinline__ uint32_t res_slot(uint64_t id) {
 }
 constexpr int kResPer = (int)kResWin / kResThreads;  // spans per thread in a packed window
 static_assert(kResWin % kResThreads == 0 && kResWin <= 65536, "window: whole rows, pos << 16 | svc");
+
+// A packed trace's slot inside its own table region of `size` slots.
+__device__ __forceinline__ uint32_t big_region_slot(uint64_t id, uint32_t size) {
+  return __umulhi((uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32), size);
+}
 
 __device__ __forceinline__ void res_out(const Table& tab, uint64_t g, uint32_t p, uint32_t sf,
                                         uint32_t dr, uint32_t S) {
@@ -1150,8 +751,9 @@ __device__ void res_one(unsigned long long* bkey, uint32_t* bval,
   __syncthreads();  // the last window's clear before the next user of the table
 }
 
-// Up to kGroup traces (bm) packed into one window, each in a private table
-// region [2 off_i, 2 off_i + 2 L_i), as big_batch.
+// Up to kGroup traces (bm: the group entries packed into this window,
+// consecutive) in one window, each in a private table region [2 off_i,
+// 2 off_i + 2 L_i).
 __device__ void res_batch(unsigned long long* bkey, uint32_t* bval,
                           const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
                           const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
@@ -1229,7 +831,7 @@ __device__ void res_batch(unsigned long long* bkey, uint32_t* bval,
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kResThreads, ANOMOD_RES_MINB) void edge_big_resolve_kernel(
+__global__ __launch_bounds__(kResThreads, kResMinWaves) void edge_big_resolve_kernel(
     const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
     const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
     const uint64_t* __restrict__ trace_ptr, uint32_t S, Table tab) {
@@ -1309,10 +911,7 @@ __global__ __launch_bounds__(kResThreads, ANOMOD_RES_MINB) void edge_big_resolve
 // The listed spans into the tables, kRecGroup traces per ticket (wave 0 keeps
 // the next ticket's entries and bounds in flight).
 constexpr int kRecGroup = 16;
-#ifndef ANOMOD_REC_PER
-#define ANOMOD_REC_PER 4
-#endif
-constexpr int kRecPer = ANOMOD_REC_PER;  // listed spans per thread loaded together
+constexpr int kRecPer = 4;  // listed spans per thread loaded together
 template <int HT, int ST>
 __global__ __launch_bounds__(kBigThreads) void edge_big_record_kernel(
     const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
@@ -1403,17 +1002,11 @@ __global__ __launch_bounds__(kThreads) void edge_agg_kernel(
   const int lane = tid & (kWave - 1);
   const int wid = tid / kWave;
   const Cols col{span_id, parent, svcfl, dur};
-#ifndef ANOMOD_DYN
-#define ANOMOD_DYN 4
-#endif
-  // Static share: the first n_static traces split evenly over the waves; with
-  // ANOMOD_DYN = d > 0 the last 1/d of the traces are handed out in segments
-  // of kDynSeg from a global counter, so waves that finish early take the tail.
-#ifndef ANOMOD_DYN_SEG
-#define ANOMOD_DYN_SEG 512
-#endif
-  constexpr uint64_t kDynSeg = ANOMOD_DYN_SEG;
-  const uint64_t n_static = ANOMOD_DYN ? n_traces - n_traces / (ANOMOD_DYN ? ANOMOD_DYN : 1) : n_traces;
+  // Static share: the first n_static traces split evenly over the waves; the
+  // last 1 / kDyn of the traces are handed out in segments of kDynSeg from a
+  // global counter, so waves that finish early take the tail.
+  constexpr uint64_t kDyn = 4, kDynSeg = 512;
+  const uint64_t n_static = n_traces - n_traces / kDyn;
   // Resume launch (compact form) after a kModeAuto launch: the trace ranges
   // its stopped waves left, then the rest of the dynamic tail.  Nothing left
   // (no workgroup saturated): return before touching LDS.
@@ -1490,7 +1083,7 @@ __global__ __launch_bounds__(kThreads) void edge_agg_kernel(
         t_next += nxt.k ? nxt.k : 1u;
         load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
       }
-      if (cur.k == 0) {  // a trace longer than kStage: listed for edge_big_kernel
+      if (cur.k == 0) {  // a trace longer than kBigMin: listed for the long-trace pass
         if (lane == 0)
           tab.big_list[atomicAdd(&tab.big[0], 1ull)] =
               tab.t_base + (MODE == kModeAuto ? *wt_cur : t_cur);
@@ -1512,7 +1105,7 @@ __global__ __launch_bounds__(kThreads) void edge_agg_kernel(
     if (next_left()) continue;
     from_left = false;
   }
-  if (!ANOMOD_DYN || n_static == n_traces) break;
+  if (n_static == n_traces) break;
   unsigned long long g = 0;
   if (lane == 0) g = atomicAdd(tab.ctr, (unsigned long long)kDynSeg);
   g = __shfl(g, 0);
@@ -1850,12 +1443,6 @@ uint64_t big_capacity(const anomod_spans* s) {
 template <int HT, int ST>
 hipError_t launch_big(anomod_ctx* ctx, const anomod_spans* spans, uint32_t S, uint32_t E,
                       const Table& tab) {
-  if (ANOMOD_BIG_ONEPASS) {  // the r02 single-kernel pass (A/B)
-    hipLaunchKernelGGL((edge_big_kernel<HT, ST>), dim3((unsigned)ctx->num_cus), dim3(kBigThreads),
-                       0, ctx->stream, spans->span_id, spans->parent_span_id, spans->svc_flags,
-                       spans->dur_us, spans->trace_ptr, S, E, tab);
-    return hipGetLastError();
-  }
   int per_cu = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
       &per_cu, reinterpret_cast<const void*>(edge_big_resolve_kernel), kResThreads, 0);

@@ -41,19 +41,6 @@
 #include "chunk.h"
 #include "common.h"
 
-#ifndef ANOMOD_SEL_TS
-#define ANOMOD_SEL_TS 0  // select-built parent scan (chunk.h find_parent_bidir SEL)
-#endif
-#ifndef ANOMOD_SPLIT_TS
-#define ANOMOD_SPLIT_TS 0  // unique-id sets: split-word scan (chunk.h find_parent_split)
-#endif
-#ifndef ANOMOD_TS_FWD
-#define ANOMOD_TS_FWD 12
-#endif
-#ifndef ANOMOD_TS_BWD
-#define ANOMOD_TS_BWD 4
-#endif
-
 namespace anomod {
 namespace {
 
@@ -107,10 +94,7 @@ struct TsOut {
 // f / l = first / last position whose id equals x (the span's own id: the
 // whole range is scanned for l), pf = first position whose id equals y (the
 // span's parent reference; -1 when y == 0).  -1 when none.
-#ifndef ANOMOD_TS_SCAN_IDS
-#define ANOMOD_TS_SCAN_IDS 10
-#endif
-constexpr uint32_t kTsScan = ANOMOD_TS_SCAN_IDS;  // ids per step (kTsScan / 2 x ds_read2_b64)
+constexpr uint32_t kTsScan = 10;  // ids per step (kTsScan / 2 x ds_read2_b64)
 
 __device__ __forceinline__ void scan_ids(const uint64_t* lsid, uint32_t a, uint32_t b, uint64_t x,
                                          uint64_t y, int& f, int& l, int& pf) {
@@ -151,9 +135,6 @@ __device__ void ts_chunk(unsigned char* wsm, int lane, const Chunk& c, uint64_t 
                          const uint64_t (&sid)[kPer], const uint64_t (&pid)[kPer],
                          const uint32_t (&svc)[kPer], const TsOut& o) {
   auto* lsid = reinterpret_cast<uint64_t*>(wsm + kTSid);
-  constexpr bool kSplit = UNI && ANOMOD_SPLIT_TS != 0;
-  auto* llo = reinterpret_cast<uint32_t*>(wsm + kTSid);  // kSplit: u32 planes in the same area
-  uint32_t* lhi = llo + (kStage + chunk::kScanSlack);
   auto* lpid = reinterpret_cast<uint64_t*>(wsm + kTPid);
   auto* lnxt = reinterpret_cast<uint32_t*>(wsm + kTNxt);
   auto* ldst = reinterpret_cast<uint32_t*>(wsm + kTDst);
@@ -167,12 +148,7 @@ __device__ void ts_chunk(unsigned char* wsm, int lane, const Chunk& c, uint64_t 
 #pragma unroll
   for (int r = 0; r < kPer; ++r) {
     const uint32_t i = lane + r * kWave;
-    if constexpr (kSplit) {
-      llo[i] = (uint32_t)sid[r];
-      lhi[i] = (uint32_t)(sid[r] >> 32);
-    } else {
-      lsid[i] = sid[r];
-    }
+    lsid[i] = sid[r];
     lpid[i] = pid[r];
     lcnt[i] = 0u;
     lsvc[i] = (uint16_t)svc[r];
@@ -206,14 +182,7 @@ __device__ void ts_chunk(unsigned char* wsm, int lane, const Chunk& c, uint64_t 
         // i), and the parent reference has at most one match, found from
         // either end (chunk.h find_parent_bidir); no own-id scan
         f[r] = l = (int)i;
-        if constexpr (kSplit)
-          pf = pid[r] != 0ull
-                   ? find_parent_split<ANOMOD_TS_FWD, ANOMOD_TS_BWD>(llo, lhi, a[r], b, i, pid[r])
-                   : -1;
-        else
-          pf = pid[r] != 0ull
-                   ? find_parent_bidir<kFwd, kBwd, 0, ANOMOD_SEL_TS != 0>(lsid, a[r], b, i, pid[r])
-                   : -1;
+        pf = pid[r] != 0ull ? find_parent_bidir<kFwd, kBwd>(lsid, a[r], b, i, pid[r]) : -1;
         np[r] = pf;
       } else {
         scan_ids(lsid, a[r], b, sid[r], pid[r], f[r], l, pf);
@@ -312,11 +281,11 @@ __device__ void ts_chunk(unsigned char* wsm, int lane, const Chunk& c, uint64_t 
     const uint32_t i = lane + r * kWave;
     if (i < c.n) {
       const uint64_t g = c.base + i;
-      st_out(&o.parent_pos[g], np[r] >= 0 ? (uint32_t)np[r] - a[r] : ANOMOD_NO_PARENT);
-      st_out(&o.depth[g], (nxt[r] & kDone) ? dst[r] : 0u);
-      st_out(&o.n_children[g], (uint32_t)lcnt[f[r]]);
-      st_out(&o.flags[g], (uint8_t)((np[r] < 0 ? ANOMOD_SPAN_ROOT : 0u) |
-                                    (f[r] == (int)i ? ANOMOD_SPAN_FIRST : 0u)));
+      o.parent_pos[g] = np[r] >= 0 ? (uint32_t)np[r] - a[r] : ANOMOD_NO_PARENT;
+      o.depth[g] = (nxt[r] & kDone) ? dst[r] : 0u;
+      o.n_children[g] = (uint32_t)lcnt[f[r]];
+      o.flags[g] = (uint8_t)((np[r] < 0 ? ANOMOD_SPAN_ROOT : 0u) |
+                             (f[r] == (int)i ? ANOMOD_SPAN_FIRST : 0u));
     }
   }
   // Per trace: lane l < k owns trace t0 + l.  Span-parallel words (complete:
@@ -649,22 +618,15 @@ __global__ __launch_bounds__(kTsThreads) __attribute__((amdgpu_waves_per_eu(4)))
     }
   }
   };
-#ifndef ANOMOD_TS_DYN
-#define ANOMOD_TS_DYN 2
-#endif
-#ifndef ANOMOD_TS_DYN_SEG
-#define ANOMOD_TS_DYN_SEG 512
-#endif
-  // As the edge kernel: a static share per wave, then the last 1/ANOMOD_TS_DYN
-  // of the traces in segments of kDynSeg from a global counter.
-  constexpr uint64_t kDynSeg = ANOMOD_TS_DYN_SEG;
-  const uint64_t n_static =
-      ANOMOD_TS_DYN ? n_traces - n_traces / (ANOMOD_TS_DYN ? ANOMOD_TS_DYN : 1) : n_traces;
+  // As the edge kernel: a static share per wave, then the last 1 / kDyn of
+  // the traces in segments of kDynSeg from a global counter.
+  constexpr uint64_t kDyn = 2, kDynSeg = 512;
+  const uint64_t n_static = n_traces - n_traces / kDyn;
   uint64_t t_begin = uniform64(n_static * gw / nw);
   uint64_t t_end = uniform64(n_static * (gw + 1) / nw);
   while (true) {
     if (t_begin < t_end) run(t_begin, t_end);
-    if (!ANOMOD_TS_DYN || n_static == n_traces) break;
+    if (n_static == n_traces) break;
     unsigned long long g = 0;
     if (lane == 0) g = atomicAdd(o.ctr, (unsigned long long)kDynSeg);
     g = __shfl(g, 0);

@@ -1,8 +1,9 @@
 """Traces longer than a wave chunk (> 256 spans), up to 2*10^5 spans in one
 trace, in shuffled in-trace order.  The chunk walk of the edge and
 trace-structure kernels lists such traces, and a workgroup-per-trace pass
-resolves them (csrc/edge_agg.hip edge_big_kernel, csrc/trace_struct.hip
-ts_big_kernel) through LDS hash windows over the trace's ids.
+resolves them (csrc/edge_agg.hip edge_big_resolve_kernel +
+edge_big_record_kernel, csrc/trace_struct.hip ts_big_kernel) through LDS hash
+windows over the trace's ids.
 
 Checker: the C oracle (ordered scans, O(L^2) per trace) up to a few thousand
 spans, with duplicated ids and cycles; beyond that the vectorised unique-id
