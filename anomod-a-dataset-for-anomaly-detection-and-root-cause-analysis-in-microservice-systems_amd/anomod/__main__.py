@@ -28,6 +28,9 @@ def main(argv=None) -> int:
     f.add_argument("--trace-step", type=float, metavar="SECONDS",
                    help="also score per-edge time series of the spans' start times, in "
                         "windows of this many seconds")
+    f.add_argument("--self-time", action="store_true",
+                   help="also compute the self-time (exclusive latency) edge table and "
+                        "write it as \"self_edges\"")
     f.add_argument("--out", help="output JSON (default: stdout)")
     j = sub.add_parser("jaeger-to-csv",
                        help="span CSV identical to jaeger_to_csv.py's (collect_trace.sh:70)")
@@ -39,7 +42,8 @@ def main(argv=None) -> int:
         return jaeger_to_csv(args.input, args.output)
 
     exp = load_experiment(args.traces, metrics=args.metrics)
-    feats = features(exp, W=args.window, trace_step_s=args.trace_step)
+    feats = features(exp, W=args.window, trace_step_s=args.trace_step,
+                     self_time=args.self_time)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -54,6 +58,8 @@ def main(argv=None) -> int:
     if feats.trace_window_scores is not None:
         doc["trace_window_scores"] = dict(zip(feats.edges.services,
                                               map(float, feats.trace_window_scores)))
+    if feats.self_edges is not None:
+        doc["self_edges"] = feats.self_edges.records()
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

@@ -436,6 +436,31 @@ class Context:
             if tmp is not None:
                 tmp.free()
 
+    def self_time(self, spans: DeviceSpans | SpanSet, with_hist: bool = True,
+                  per_span: bool = False):
+        """Self-time (exclusive latency) edge table of a grouped set
+        (anomod_edge_self_time_spans): the rows, counts and errors of
+        edge_aggregate, the latency fields over self_us = dur_us - min(dur_us,
+        sum of the direct children's dur_us).  per_span=True also returns the
+        u32 self_us column by span position (rank-local).  A host set is
+        uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            table = EdgeTable.empty(spans.services, with_hist)
+            cs = table.c_struct()
+            self_us = np.zeros(spans.n_spans, np.uint32) if per_span else None
+            self._check(self._lib.anomod_edge_self_time_spans(
+                self.handle, spans.handle, S, C.byref(cs), L.ptr(self_us, C.c_uint32)))
+            if table.hist is not None:
+                table.hist = table.hist.reshape(edge_rows(S), L.HIST_BINS)
+            return (table, self_us) if per_span else table
+        finally:
+            if tmp is not None:
+                tmp.free()
+
     def edge_quantiles_exact(self, spans: DeviceSpans | SpanSet, q_pct=(50, 99)):
         """Exact per-edge order statistics x[(c*q)//100] of the sorted edge
         latencies ([E, len(q_pct)], NaN for empty edges) and the per-edge

@@ -165,6 +165,8 @@ class Features:
     # trace anomaly scores taken from it
     edge_windows: EdgeWindows | None = None
     trace_window_scores: np.ndarray | None = None
+    # features(self_time=True): the self-time (exclusive latency) edge table
+    self_edges: EdgeTable | None = None
 
 
 _default_ctx: Context | None = None
@@ -268,13 +270,19 @@ def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: flo
 def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              alpha: float | None = None, eps: float = 1e-12, with_hist: bool = True,
              baseline: "Features | None" = None, trace_step_s: float | None = None,
-             trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5) -> Features:
+             trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5,
+             self_time: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
-    the score gains 0.25 * ts / (1 + ts)."""
+    the score gains 0.25 * ts / (1 + ts).  With self_time the result also
+    holds the self-time edge table (Context.self_time), and the latency term
+    against a baseline that has one is the p99 growth of self time instead of
+    the inclusive duration (components["latency_kind"] says which), so a slow
+    service no longer raises the term of its callers."""
     ctx = ctx or default_context()
     edges = ctx.edge_aggregate(exp.spans, with_hist=with_hist)
+    self_edges = ctx.self_time(exp.spans, with_hist=with_hist) if self_time else None
     S = edges.n_services
     alpha = 2.0 / (W + 1) if alpha is None else alpha
     Z = None
@@ -306,21 +314,26 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     err = edges.errors.reshape(S + 2, S).sum(axis=0).astype(np.float64)
     err_rate = np.divide(err, cnt, out=np.zeros(S), where=cnt > 0)
     lat = np.zeros(S)
-    if baseline is not None:
+    use_self = self_edges is not None and baseline is not None and baseline.self_edges is not None
+    if use_self:
+        lat = _latency_shift(self_edges, baseline.self_edges)
+    elif baseline is not None:
         lat = _latency_shift(edges, baseline.edges)
     ms = metric_score / (1.0 + metric_score)  # squash z into [0, 1)
     score = err_rate + lat + 0.25 * ms
     params = {"W": W, "alpha": alpha, "eps": eps,
               "components": {"error_rate": err_rate, "latency": lat, "metric": ms}}
+    if self_time:
+        params["components"]["latency_kind"] = "self" if use_self else "inclusive"
     if trace_step_s is None:
-        return Features(exp.name, edges, Z, series, score, params)
+        return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
     params["components"]["trace"] = tsq
     params.update(trace_step_s=trace_step_s, trace_W=trace_W, trace_eps=trace_eps,
                   trace_min_count=trace_min_count)
     return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
-                    edge_windows=win, trace_window_scores=ts)
+                    edge_windows=win, trace_window_scores=ts, self_edges=self_edges)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

@@ -234,6 +234,12 @@ int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uin
 size_t span_edge_keys_ws_bytes(const anomod_spans* s);
 int span_edge_keys(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, unsigned long long* keys,
                    unsigned long long* ws);
+// The parent scan the edge kernels use for a grouped set (edge_agg.hip):
+// *unique = the scans from both ends apply (ids declared unique, collector
+// order).  An unknown order hint is probed first, as at the set's first
+// aggregation (d_cnt: two device words; one small kernel and a host wait).
+int span_scan_choice(anomod_ctx* ctx, const anomod_spans* s, unsigned long long* d_cnt,
+                     bool* unique);
 // Grow-only device workspace owned by the ctx.
 int ensure_table(anomod_ctx* ctx, size_t bytes);
 enum ScratchSlot { kScratchQuantiles = 0, kScratchTraceStruct = 1, kScratchTsLong = 2,

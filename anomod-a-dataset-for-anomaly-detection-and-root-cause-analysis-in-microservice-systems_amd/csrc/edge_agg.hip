@@ -1624,6 +1624,13 @@ int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uin
   return ANOMOD_OK;
 }
 
+int span_scan_choice(anomod_ctx* ctx, const anomod_spans* s, unsigned long long* d_cnt,
+                     bool* unique) {
+  if (int rc = probe_order(ctx, s, d_cnt)) return rc;
+  *unique = use_unique(s);
+  return ANOMOD_OK;
+}
+
 // ws words: [0] dynamic-tail counter, [1..3] long-trace counters, [4..5] order
 // probe, [32..] long-trace list.
 size_t span_edge_keys_ws_bytes(const anomod_spans* s) { return 256 + big_capacity(s) * 8; }

@@ -405,6 +405,26 @@ typedef struct {
 } anomod_edge_windows;
 int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               anomod_edge_windows* out);
+/* Self-time (exclusive latency) edge table of a grouped set.  The parent of
+ * span i is the first span of its trace, in position order, whose span_id
+ * equals i's parent_span_id — the edge table's rule, duplicated ids
+ * included; a root (reference 0), an orphan (no such span) and a span whose
+ * first match is itself have none.  With child_sum(j) the u64 sum of dur_us
+ * over the spans whose parent is j,
+ *   self_us[i] = dur_us[i] - min(dur_us[i], child_sum(i))
+ * (children that overlap in time are summed, not merged: a fan-out parent
+ * saturates to 0).  `out` has the layout and rows of the edge table of
+ * anomod_edge_aggregate_spans — a self-referencing span sits in the row that
+ * table gives it — with sum / min / max / hist / p50 / p99 taken over self_us;
+ * count and errors equal that table's.  Every result is an integer, bit-exact
+ * for any launch geometry.  NULL outputs are skipped; n == 0 gives an empty
+ * table; a service index >= n_services is ANOMOD_EINVAL, an ungrouped set
+ * ANOMOD_ESTATE; at most 2^32 - 2 spans per call.  With a communicator
+ * attached the table is merged over the ranks and self_us stays rank-local.
+ * The set's histogram-form hint is neither read nor changed.                */
+int anomod_edge_self_time_spans(anomod_ctx* ctx, const anomod_spans* spans, uint32_t n_services,
+                                anomod_edge_table* out,
+                                uint32_t* self_us /* [n_spans] host, may be NULL */);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
