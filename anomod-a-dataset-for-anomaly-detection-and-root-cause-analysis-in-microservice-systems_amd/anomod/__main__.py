@@ -1,4 +1,5 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
+                                 [--spectrum] [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
 Computes the RCA features of one experiment on the GPU and writes them as JSON:
@@ -31,6 +32,12 @@ def main(argv=None) -> int:
     f.add_argument("--self-time", action="store_true",
                    help="also compute the self-time (exclusive latency) edge table and "
                         "write it as \"self_edges\"")
+    f.add_argument("--spectrum", action="store_true",
+                   help="also label the traces abnormal / normal and write the per-service "
+                        "trace coverage and Ochiai coefficients as \"spectrum\"")
+    f.add_argument("--baseline", metavar="TRACES",
+                   help="trace file (or dir) of a normal run: its features are the baseline "
+                        "of the latency term and of the spectrum's latency thresholds")
     f.add_argument("--out", help="output JSON (default: stdout)")
     j = sub.add_parser("jaeger-to-csv",
                        help="span CSV identical to jaeger_to_csv.py's (collect_trace.sh:70)")
@@ -42,8 +49,12 @@ def main(argv=None) -> int:
         return jaeger_to_csv(args.input, args.output)
 
     exp = load_experiment(args.traces, metrics=args.metrics)
+    baseline = None
+    if args.baseline:
+        baseline = features(load_experiment(args.baseline), W=args.window,
+                            self_time=args.self_time)
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
-                     self_time=args.self_time)
+                     self_time=args.self_time, baseline=baseline, spectrum=args.spectrum)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -60,6 +71,17 @@ def main(argv=None) -> int:
                                               map(float, feats.trace_window_scores)))
     if feats.self_edges is not None:
         doc["self_edges"] = feats.self_edges.records()
+    if feats.spectrum is not None:
+        sp = feats.spectrum
+        names = feats.edges.services
+        doc["spectrum"] = {
+            "thresholds": feats.params["components"]["spectrum_thresholds"],
+            "traces": {"normal": int(sp.n_traces[0]), "abnormal": int(sp.n_traces[1])},
+            "service_traces": {s: {"normal": int(sp.svc_traces[0, i]),
+                                   "abnormal": int(sp.svc_traces[1, i])}
+                               for i, s in enumerate(names)},
+            "ochiai": dict(zip(names, map(float, sp.ochiai()))),
+        }
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

@@ -86,6 +86,19 @@ class EdgeWindowsC(C.Structure):
     ]
 
 
+class TraceSpectrumC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("use_errors", C.c_uint32),
+        ("thr_us", C.POINTER(C.c_uint32)),
+        ("n_traces", C.c_uint64 * 2),
+        ("svc_traces", C.POINTER(C.c_uint64)),
+        ("edge_traces", C.POINTER(C.c_uint64)),
+        ("bad_spans", C.POINTER(C.c_uint64)),
+        ("trace_abnormal", C.POINTER(C.c_uint8)),
+    ]
+
+
 class TraceStructC(C.Structure):
     _fields_ = [
         ("n_services", C.c_uint32),
@@ -199,6 +212,7 @@ _SIGS = {
     "anomod_spans_generate": (_i32, [_vp, _P(SynthSpec), _u64, _u64, _P(_vp)]),
     "anomod_edge_aggregate_spans": (_i32, [_vp, _vp, _u32, _P(EdgeTableC)]),
     "anomod_edge_self_time_spans": (_i32, [_vp, _vp, _u32, _P(EdgeTableC), _P(C.c_uint32)]),
+    "anomod_trace_spectrum_spans": (_i32, [_vp, _vp, _P(TraceSpectrumC)]),
     "anomod_edge_aggregate_host": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _u32, _i32,
                                           _P(_i32), _P(_i32), _P(EdgeTableC)]),
     "anomod_edge_aggregate": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _P(EdgeTableC)]),

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import EdgeTable, EdgeWindows, SpanSet, TraceStructure, edge_rows
+from .spans import EdgeTable, EdgeWindows, SpanSet, TraceSpectrum, TraceStructure, edge_rows
 
 
 @dataclass
@@ -457,6 +457,42 @@ class Context:
             if table.hist is not None:
                 table.hist = table.hist.reshape(edge_rows(S), L.HIST_BINS)
             return (table, self_us) if per_span else table
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def trace_spectrum(self, spans: DeviceSpans | SpanSet, thr_us=None, use_errors: bool = True,
+                       per_trace: bool = True) -> TraceSpectrum:
+        """Abnormal / normal trace labels and the per-class trace coverage of
+        services and edge rows (anomod_trace_spectrum_spans).  thr_us: u32 [E]
+        latency thresholds by edge row (spectrum_thresholds; None: none, only
+        error flags label traces).  per_trace=False skips the per-trace class
+        column.  Rank-local.  A host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            E = edge_rows(S)
+            thr = None
+            if thr_us is not None:
+                thr = np.ascontiguousarray(thr_us, np.uint32)
+                if thr.shape != (E,):
+                    raise ValueError(f"thr_us has shape {thr.shape}, expected ({E},)")
+            sp = TraceSpectrum(list(spans.services), np.zeros(2, np.uint64),
+                               np.zeros((2, S), np.uint64), np.zeros((2, E), np.uint64),
+                               np.zeros(E, np.uint64),
+                               np.zeros(spans.n_traces, np.uint8) if per_trace else None, thr,
+                               bool(use_errors))
+            cs = L.TraceSpectrumC(S, 1 if use_errors else 0, L.ptr(thr, C.c_uint32), (0, 0),
+                                  L.ptr(sp.svc_traces, C.c_uint64),
+                                  L.ptr(sp.edge_traces, C.c_uint64),
+                                  L.ptr(sp.bad_spans, C.c_uint64),
+                                  L.ptr(sp.trace_abnormal, C.c_uint8))
+            self._check(self._lib.anomod_trace_spectrum_spans(self.handle, spans.handle,
+                                                              C.byref(cs)))
+            sp.n_traces[:] = (cs.n_traces[0], cs.n_traces[1])
+            return sp
         finally:
             if tmp is not None:
                 tmp.free()

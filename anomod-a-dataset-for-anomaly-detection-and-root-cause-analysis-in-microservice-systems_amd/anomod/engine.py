@@ -23,7 +23,7 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import EdgeTable, EdgeWindows, SpanSet, edge_rows
+from .spans import EdgeTable, EdgeWindows, SpanSet, TraceSpectrum, edge_rows, spectrum_thresholds
 
 # --------------------------------------------------------------------------
 # Ground-truth labels (experiment name -> faulty service), SURVEY.md §2:
@@ -167,6 +167,8 @@ class Features:
     trace_window_scores: np.ndarray | None = None
     # features(self_time=True): the self-time (exclusive latency) edge table
     self_edges: EdgeTable | None = None
+    # features(spectrum=True): abnormal / normal trace labels and coverage
+    spectrum: TraceSpectrum | None = None
 
 
 _default_ctx: Context | None = None
@@ -271,7 +273,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              alpha: float | None = None, eps: float = 1e-12, with_hist: bool = True,
              baseline: "Features | None" = None, trace_step_s: float | None = None,
              trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5,
-             self_time: bool = False) -> Features:
+             self_time: bool = False, spectrum: bool = False,
+             spectrum_rows: str = "root") -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -279,7 +282,12 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     holds the self-time edge table (Context.self_time), and the latency term
     against a baseline that has one is the p99 growth of self time instead of
     the inclusive duration (components["latency_kind"] says which), so a slow
-    service no longer raises the term of its callers."""
+    service no longer raises the term of its callers.  With spectrum the
+    traces are labelled abnormal / normal (Context.trace_spectrum: latency
+    thresholds from baseline.edges by spectrum_thresholds(rows=spectrum_rows)
+    when a baseline is given, else error flags alone —
+    components["spectrum_thresholds"] says which) and the score gains 0.25 *
+    the per-service Ochiai coefficient of the trace coverage."""
     ctx = ctx or default_context()
     edges = ctx.edge_aggregate(exp.spans, with_hist=with_hist)
     self_edges = ctx.self_time(exp.spans, with_hist=with_hist) if self_time else None
@@ -325,15 +333,26 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
               "components": {"error_rate": err_rate, "latency": lat, "metric": ms}}
     if self_time:
         params["components"]["latency_kind"] = "self" if use_self else "inclusive"
+    spec = None
+    if spectrum:
+        thr = (spectrum_thresholds(baseline.edges, edges.services, rows=spectrum_rows)
+               if baseline is not None else None)
+        spec = ctx.trace_spectrum(exp.spans, thr_us=thr)
+        och = spec.ochiai()
+        params["components"]["spectrum"] = och
+        params["components"]["spectrum_thresholds"] = "baseline" if thr is not None else "errors-only"
+        score = score + 0.25 * och
     if trace_step_s is None:
-        return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges)
+        return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
+                        spectrum=spec)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
     params["components"]["trace"] = tsq
     params.update(trace_step_s=trace_step_s, trace_W=trace_W, trace_eps=trace_eps,
                   trace_min_count=trace_min_count)
     return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
-                    edge_windows=win, trace_window_scores=ts, self_edges=self_edges)
+                    edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
+                    spectrum=spec)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

@@ -301,6 +301,69 @@ class EdgeWindows:
         return MetricMatrix(X, ts, series)
 
 
+U32_MAX = 0xFFFFFFFF
+
+
+def _ochiai(ef: np.ndarray, ep: np.ndarray, F: int) -> np.ndarray:
+    """ef / sqrt(F * (ef + ep)) in float64, 0 where the denominator is 0."""
+    ef = ef.astype(np.float64)
+    den = np.sqrt(float(F) * (ef + ep.astype(np.float64)))
+    return np.divide(ef, den, out=np.zeros(ef.shape[0]), where=den > 0)
+
+
+@dataclass
+class TraceSpectrum:
+    """Abnormal / normal trace labels of a span set and the per-class trace
+    coverage of services and edge rows (anomod_trace_spectrum_spans): a span
+    is bad when dur_us > thr_us[its edge row] or, with use_errors, when it
+    carries the error flag; a trace is abnormal (class 1) when any of its
+    spans is bad.  Rows as in EdgeTable."""
+
+    services: list[str]
+    n_traces: np.ndarray              # u64 [2] traces per class
+    svc_traces: np.ndarray            # u64 [2, S] traces of the class holding the service
+    edge_traces: np.ndarray           # u64 [2, E] the same per edge row
+    bad_spans: np.ndarray             # u64 [E] bad spans per row
+    trace_abnormal: np.ndarray | None  # u8 [n_traces] class of each trace
+    thr_us: np.ndarray | None         # u32 [E] the thresholds used (None: none)
+    use_errors: bool = True
+
+    def ochiai(self) -> np.ndarray:
+        """Per service: ef / sqrt(F * (ef + ep)) with ef / ep the abnormal /
+        normal traces holding the service and F the abnormal traces."""
+        return _ochiai(self.svc_traces[1], self.svc_traces[0], int(self.n_traces[1]))
+
+    def edge_ochiai(self) -> np.ndarray:
+        """ochiai() per edge row."""
+        return _ochiai(self.edge_traces[1], self.edge_traces[0], int(self.n_traces[1]))
+
+
+def spectrum_thresholds(base: EdgeTable, services: list[str], *, rows: str = "root",
+                        min_count: int = 10) -> np.ndarray:
+    """Latency thresholds (u32 [E] over `services`) for Context.trace_spectrum
+    from a baseline run's edge table: floor(base.p99_us) of the same edge —
+    matched by service NAMES, as the latency term matches them — where the
+    baseline edge holds >= min_count spans and a finite p99, else UINT32_MAX
+    (never fires).  rows="root" sets only the ROOT rows (trace entry spans: their
+    duration is the trace's end-to-end latency), rows="all" every row."""
+    if rows not in ("root", "all"):
+        raise ValueError(f"rows={rows!r}: 'root' or 'all'")
+    S, Sb = len(services), base.n_services
+    pos = {s: i for i, s in enumerate(base.services)}
+    m = np.array([pos.get(s, -1) for s in services] + [Sb, Sb + 1], np.int64)  # + ROOT, ORPHAN
+    p_cur = np.repeat(np.arange(S + 2), S)
+    pb, cb = m[p_cur], m[np.tile(np.arange(S), S + 2)]
+    have = (pb >= 0) & (cb >= 0)
+    if rows == "root":
+        have &= p_cur == S
+    brow = np.where(have, pb * Sb + cb, 0)
+    p99 = np.where(have, base.p99_us[brow], np.nan)
+    ok = have & (base.count[brow] >= min_count) & np.isfinite(p99)
+    thr = np.full(edge_rows(S), U32_MAX, np.uint32)
+    thr[ok] = np.minimum(np.floor(p99[ok]), float(U32_MAX)).astype(np.uint32)
+    return thr
+
+
 @dataclass
 class TraceStructure:
     """Per-span / per-trace structure of a span set (trace_collector.py:401-481,

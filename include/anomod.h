@@ -425,6 +425,39 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
 int anomod_edge_self_time_spans(anomod_ctx* ctx, const anomod_spans* spans, uint32_t n_services,
                                 anomod_edge_table* out,
                                 uint32_t* self_us /* [n_spans] host, may be NULL */);
+/* Trace spectrum of a grouped set: every trace is labelled normal (class 0)
+ * or abnormal (class 1), and per class the traces that pass through each
+ * service and each edge row are counted.  With row(i) the edge row
+ * anomod_edge_aggregate_spans counts span i in (duplicated ids, orphans and
+ * self-references land where that table puts them),
+ *   bad(i) = dur_us[i] > thr_us[row(i)]                      (strict)
+ *            || use_errors && (flags[i] & ANOMOD_FLAG_ERROR)
+ * and trace t is abnormal when any of its spans is bad.  thr_us[r] ==
+ * UINT32_MAX never fires; thr_us == NULL stands for UINT32_MAX in every row.
+ * An empty trace is normal and covers nothing.  svc_traces[k][s] counts the
+ * traces of class k holding at least one span of service s (a trace counts
+ * once per service), edge_traces[k][r] the same per edge row, bad_spans[r]
+ * every bad span of row r.  Every result is an integer, bit-exact for any
+ * launch geometry.  NULL outputs are skipped; n == 0 gives zeros (every trace
+ * normal); an ungrouped set is ANOMOD_ESTATE; a service index >= n_services
+ * or E = (S + 2) * S > 2^19 (S >= 724: the long-trace pass keeps one bit per
+ * row in 64 KiB of LDS) is ANOMOD_EINVAL; at most 2^32 - 2 spans per call.
+ * The call is rank-local: no collective runs even with a communicator
+ * attached (a caller sums the ranks' integer tables itself).  The set's hints
+ * are read and updated only as anomod_edge_windows_spans does (the order
+ * probe of a first walk).                                                   */
+typedef struct {
+  uint32_t n_services;     /* in : S; E = (S + 2) * S as in anomod_edge_table    */
+  uint32_t use_errors;     /* in : non-zero: an error-flagged span is bad        */
+  const uint32_t* thr_us;  /* in : [E] host latency thresholds, or NULL          */
+  uint64_t n_traces[2];    /* out: traces per class                              */
+  uint64_t* svc_traces;    /* [2 * S] host, class-major; each may be NULL        */
+  uint64_t* edge_traces;   /* [2 * E] host, class-major                          */
+  uint64_t* bad_spans;     /* [E] host                                           */
+  uint8_t* trace_abnormal; /* [n_traces] host: the class of every trace          */
+} anomod_trace_spectrum;
+int anomod_trace_spectrum_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                                anomod_trace_spectrum* out);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
