@@ -608,6 +608,8 @@ class DeviceGraph:
             row_ptr = np.ascontiguousarray(row_ptr, np.uint32)
             col = np.ascontiguousarray(col, np.uint32)
             w = np.ascontiguousarray(w, np.float32)
+            if col.size == 0:  # keep the pointers valid for an edgeless graph
+                col, w = np.zeros(1, np.uint32), np.zeros(1, np.float32)
             ctx._check(lib.anomod_graph_create(ctx.handle, L.ptr(row_ptr, C.c_uint32),
                                                L.ptr(col, C.c_uint32), L.ptr(w, C.c_float),
                                                row_ptr.shape[0] - 1, C.byref(h)))

@@ -1273,7 +1273,9 @@ int anomod_graph_create(anomod_ctx* ctx, const uint32_t* row_ptr, const uint32_t
     for (uint32_t k = row_ptr[u]; k < row_ptr[u + 1]; ++k) {
       const uint32_t pos = fill[col[k]]++;
       in_col[pos] = u;
-      in_w[pos] = (float)((double)w[k] / outw[u]);
+      // a row whose weights sum to 0 is dangling: its edges carry nothing
+      // (0 / 0 would put NaN into every callee)
+      in_w[pos] = dang[u] ? 0.f : (float)((double)w[k] / outw[u]);
     }
   }
   if (int rc = bind(ctx)) return rc;

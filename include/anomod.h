@@ -602,6 +602,9 @@ int anomod_series_free(anomod_series* ser);
  * weights; rows are normalised by out-weight; dangling mass is sent along
  * the personalization p; x0 = 1/N;
  *   x <- alpha*(x A + sum_{dangling} x * p) + (1 - alpha)*p
+ * A row whose weights sum to 0 (no edges, or only zero-weight edges) is
+ * dangling: its edges contribute nothing.  Every other edge weight is
+ * (float)((double)w / out-weight), the out-weight summed in double.
  * stop when ||x - x_last||_1 < N*tol (tol > 0) or after `iters` iterations.
  * iters_done = iterations executed; status ANOMOD_OK even when tol was not
  * reached (caller checks iters_done == iters).                            */
