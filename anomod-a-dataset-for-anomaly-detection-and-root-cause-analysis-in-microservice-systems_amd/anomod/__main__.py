@@ -1,5 +1,6 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
-                                 [--spectrum] [--baseline <trace file|dir>]
+                                 [--spectrum] [--critical-path]
+                                 [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
 Computes the RCA features of one experiment on the GPU and writes them as JSON:
@@ -35,6 +36,10 @@ def main(argv=None) -> int:
     f.add_argument("--spectrum", action="store_true",
                    help="also label the traces abnormal / normal and write the per-service "
                         "trace coverage and Ochiai coefficients as \"spectrum\"")
+    f.add_argument("--critical-path", action="store_true",
+                   help="also compute the critical-path edge table (the spans that determined "
+                        "each trace's end-to-end latency and the exclusive time each added; "
+                        "needs span start times) and write it as \"cp_edges\"")
     f.add_argument("--baseline", metavar="TRACES",
                    help="trace file (or dir) of a normal run: its features are the baseline "
                         "of the latency term and of the spectrum's latency thresholds")
@@ -52,9 +57,10 @@ def main(argv=None) -> int:
     baseline = None
     if args.baseline:
         baseline = features(load_experiment(args.baseline), W=args.window,
-                            self_time=args.self_time)
+                            self_time=args.self_time, critical_path=args.critical_path)
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
-                     self_time=args.self_time, baseline=baseline, spectrum=args.spectrum)
+                     self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
+                     critical_path=args.critical_path)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -71,6 +77,9 @@ def main(argv=None) -> int:
                                               map(float, feats.trace_window_scores)))
     if feats.self_edges is not None:
         doc["self_edges"] = feats.self_edges.records()
+    if feats.cp_edges is not None:
+        doc["cp_edges"] = feats.cp_edges.records()
+        doc["latency_kind"] = feats.params["components"]["latency_kind"]
     if feats.spectrum is not None:
         sp = feats.spectrum
         names = feats.edges.services

@@ -212,6 +212,8 @@ _SIGS = {
     "anomod_spans_generate": (_i32, [_vp, _P(SynthSpec), _u64, _u64, _P(_vp)]),
     "anomod_edge_aggregate_spans": (_i32, [_vp, _vp, _u32, _P(EdgeTableC)]),
     "anomod_edge_self_time_spans": (_i32, [_vp, _vp, _u32, _P(EdgeTableC), _P(C.c_uint32)]),
+    "anomod_edge_critical_path_spans": (_i32, [_vp, _vp, _u32, _P(EdgeTableC), _P(C.c_uint32),
+                                               _P(C.c_uint8)]),
     "anomod_trace_spectrum_spans": (_i32, [_vp, _vp, _P(TraceSpectrumC)]),
     "anomod_edge_aggregate_host": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _u32, _i32,
                                           _P(_i32), _P(_i32), _P(EdgeTableC)]),

@@ -11,7 +11,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import EdgeTable, EdgeWindows, SpanSet, TraceSpectrum, TraceStructure, edge_rows
+from .spans import (CriticalPath, EdgeTable, EdgeWindows, SpanSet, TraceSpectrum, TraceStructure,
+                    edge_rows)
 
 
 @dataclass
@@ -457,6 +458,37 @@ class Context:
             if table.hist is not None:
                 table.hist = table.hist.reshape(edge_rows(S), L.HIST_BINS)
             return (table, self_us) if per_span else table
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def critical_path(self, spans: DeviceSpans | SpanSet, with_hist: bool = True,
+                      per_span: bool = False) -> CriticalPath:
+        """Critical path of a grouped set with start times
+        (anomod_edge_critical_path_spans): which spans determined their
+        trace's end-to-end latency (walking back from each parent's end
+        through its last-finishing, non-overlapping children) and the
+        exclusive time each added; the edge table counts the on-path spans
+        and takes its latency fields over their cp_us.  per_span=True also
+        returns the u32 cp_us and u8 on_path columns by span position
+        (rank-local).  A host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            if spans.start_us is None:
+                raise ValueError("span set has no start_us column")
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            table = EdgeTable.empty(spans.services, with_hist)
+            cs = table.c_struct()
+            cp_us = np.zeros(spans.n_spans, np.uint32) if per_span else None
+            on_path = np.zeros(spans.n_spans, np.uint8) if per_span else None
+            self._check(self._lib.anomod_edge_critical_path_spans(
+                self.handle, spans.handle, S, C.byref(cs), L.ptr(cp_us, C.c_uint32),
+                L.ptr(on_path, C.c_uint8)))
+            if table.hist is not None:
+                table.hist = table.hist.reshape(edge_rows(S), L.HIST_BINS)
+            return CriticalPath(table, cp_us, on_path)
         finally:
             if tmp is not None:
                 tmp.free()

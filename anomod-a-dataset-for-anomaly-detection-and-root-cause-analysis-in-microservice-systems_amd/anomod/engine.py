@@ -169,6 +169,8 @@ class Features:
     self_edges: EdgeTable | None = None
     # features(spectrum=True): abnormal / normal trace labels and coverage
     spectrum: TraceSpectrum | None = None
+    # features(critical_path=True): the critical-path edge table
+    cp_edges: EdgeTable | None = None
 
 
 _default_ctx: Context | None = None
@@ -274,7 +276,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              baseline: "Features | None" = None, trace_step_s: float | None = None,
              trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5,
              self_time: bool = False, spectrum: bool = False,
-             spectrum_rows: str = "root") -> Features:
+             spectrum_rows: str = "root", critical_path: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -287,10 +289,18 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     thresholds from baseline.edges by spectrum_thresholds(rows=spectrum_rows)
     when a baseline is given, else error flags alone —
     components["spectrum_thresholds"] says which) and the score gains 0.25 *
-    the per-service Ochiai coefficient of the trace coverage."""
+    the per-service Ochiai coefficient of the trace coverage.  With
+    critical_path (the span set needs start_us) the result also holds the
+    critical-path edge table (Context.critical_path), and against a baseline
+    that has one the latency term is the p99 growth of the time spans add on
+    the critical path (latency_kind "critical", ahead of "self" and
+    "inclusive"): a span that merely runs beside a longer sibling no longer
+    raises it, and a fan-out parent's own work does."""
     ctx = ctx or default_context()
     edges = ctx.edge_aggregate(exp.spans, with_hist=with_hist)
     self_edges = ctx.self_time(exp.spans, with_hist=with_hist) if self_time else None
+    cp_edges = (ctx.critical_path(exp.spans, with_hist=with_hist).edges if critical_path
+                else None)
     S = edges.n_services
     alpha = 2.0 / (W + 1) if alpha is None else alpha
     Z = None
@@ -323,7 +333,10 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     err_rate = np.divide(err, cnt, out=np.zeros(S), where=cnt > 0)
     lat = np.zeros(S)
     use_self = self_edges is not None and baseline is not None and baseline.self_edges is not None
-    if use_self:
+    use_cp = cp_edges is not None and baseline is not None and baseline.cp_edges is not None
+    if use_cp:
+        lat = _latency_shift(cp_edges, baseline.cp_edges)
+    elif use_self:
         lat = _latency_shift(self_edges, baseline.self_edges)
     elif baseline is not None:
         lat = _latency_shift(edges, baseline.edges)
@@ -331,8 +344,9 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     score = err_rate + lat + 0.25 * ms
     params = {"W": W, "alpha": alpha, "eps": eps,
               "components": {"error_rate": err_rate, "latency": lat, "metric": ms}}
-    if self_time:
-        params["components"]["latency_kind"] = "self" if use_self else "inclusive"
+    if self_time or critical_path:
+        params["components"]["latency_kind"] = ("critical" if use_cp else
+                                                "self" if use_self else "inclusive")
     spec = None
     if spectrum:
         thr = (spectrum_thresholds(baseline.edges, edges.services, rows=spectrum_rows)
@@ -344,7 +358,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         score = score + 0.25 * och
     if trace_step_s is None:
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
-                        spectrum=spec)
+                        spectrum=spec, cp_edges=cp_edges)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
     params["components"]["trace"] = tsq
@@ -352,7 +366,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
                   trace_min_count=trace_min_count)
     return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
-                    spectrum=spec)
+                    spectrum=spec, cp_edges=cp_edges)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

@@ -301,6 +301,26 @@ class EdgeWindows:
         return MetricMatrix(X, ts, series)
 
 
+@dataclass
+class CriticalPath:
+    """Critical path of a span set with start times
+    (anomod_edge_critical_path_spans): the edge table of the on-path spans
+    over their cp_us (exclusive time on the path) and, when asked for, the
+    per-span columns by span position."""
+
+    edges: EdgeTable
+    cp_us: np.ndarray | None = None     # u32 [n_spans]
+    on_path: np.ndarray | None = None   # u8  [n_spans]
+
+    def service_share(self) -> np.ndarray:
+        """Per child service: its share of the critical-path time of the whole
+        table (zeros for an empty table)."""
+        S = self.edges.n_services
+        per = self.edges.sum_us.reshape(S + 2, S).sum(axis=0).astype(np.float64)
+        tot = per.sum()
+        return per / tot if tot > 0 else np.zeros(S)
+
+
 U32_MAX = 0xFFFFFFFF
 
 

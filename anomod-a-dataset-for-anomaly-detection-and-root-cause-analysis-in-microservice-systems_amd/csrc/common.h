@@ -221,8 +221,10 @@ void free_group_ws(anomod_ctx* ctx);
 int upload_items(anomod_ctx* ctx, const UpItem* items, int n_items, uint32_t* max_svc);
 void free_uploader(anomod_ctx* ctx);
 // Edge table of n per-span edge records (the fused ungrouped aggregation:
-// (parent row * S + service) << 33 | error << 32 | duration, csrc/bucket.hip)
-// into `out`, merged over an attached communicator; *hist_form is the set's
+// (parent row * S + service) << 33 | error << 32 | duration, csrc/bucket.hip;
+// a record of all ones is no span and is skipped: critical_path.hip writes it
+// for the spans off the path) into `out`, merged over an attached
+// communicator; *hist_form is the set's
 // histogram-form hint (read, and updated with what the run learned).
 int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uint32_t S,
                            int8_t* hist_form, anomod_edge_table* out);

@@ -1121,9 +1121,10 @@ __global__ __launch_bounds__(kThreads) void edge_agg_kernel(
 // Edge records (the fused ungrouped aggregation, bucket.hip): one 8-B record
 // per span — (parent row * S + service) << 33 | error << 32 | duration — into
 // the chunk walk's LDS table forms.  A plain stream: 8 records per thread
-// loaded together, then recorded.  The compact form also reports its largest
-// workgroup occupancy (tab.ovf[1], atomic max), so a set learns whether the
-// pair table would hold it.
+// loaded together, then recorded; a record of all ones (the padding past n,
+// and a caller's "no span here": common.h) is skipped.  The compact form also
+// reports its largest workgroup occupancy (tab.ovf[1], atomic max), so a set
+// learns whether the pair table would hold it.
 constexpr int kRecLoad = 8;
 template <int HT, int ST>
 __global__ __launch_bounds__(kThreads) void edge_rec_kernel(const uint64_t* __restrict__ rec,

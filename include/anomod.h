@@ -425,6 +425,34 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
 int anomod_edge_self_time_spans(anomod_ctx* ctx, const anomod_spans* spans, uint32_t n_services,
                                 anomod_edge_table* out,
                                 uint32_t* self_us /* [n_spans] host, may be NULL */);
+/* Critical path of a grouped set with a start-time column, and its edge
+ * table: which spans determined the end-to-end latency of their trace, and
+ * how much each added.  With s(i) = start_us[i], e(i) = s(i) + dur_us[i]
+ * (u64, saturating) and par(i) the parent rule of the self-time call, a span
+ * of a trace without a parent is a head (roots, orphans, self-references).
+ * A child c of p = par(c) covers [a, b) = [max(s(c), s(p)), min(e(c), e(p)))
+ * and is eligible when a < b.  The selection at p starts at cur = e(p) and
+ * repeatedly takes, among the eligible children with b <= cur, the one with
+ * the largest b (the smallest position among equal b), selects it and
+ * continues at cur = a of it.  on_path is the least set holding every head
+ * and every selected span whose parent is on the path (a span whose parent
+ * chain never reaches a head — a reference cycle — is off it), and
+ *   cp_us[i] = dur_us[i] - sum of (b - a) over the selected children of i
+ * for i on the path, 0 otherwise.  `out` has the layout and rows of the edge
+ * table of anomod_edge_aggregate_spans; count and errors are taken over the
+ * on-path spans only, sum / min / max / hist / p50 / p99 over their cp_us.
+ * Every result is an integer, bit-exact for any launch geometry.  NULL
+ * outputs are skipped; n == 0 gives an empty table; spans outside every
+ * trace read 0 / 0; a service index >= n_services is ANOMOD_EINVAL, a set
+ * without a start column or an ungrouped set ANOMOD_ESTATE; at most 2^32 - 2
+ * spans per call.  With a communicator attached the table is merged over the
+ * ranks, cp_us and on_path stay rank-local.  The set's histogram-form hint
+ * is neither read nor changed; an unknown order hint is probed as in the
+ * self-time call.                                                           */
+int anomod_edge_critical_path_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                                    uint32_t n_services, anomod_edge_table* out,
+                                    uint32_t* cp_us /* [n_spans] host, may be NULL */,
+                                    uint8_t* on_path /* [n_spans] host, may be NULL */);
 /* Trace spectrum of a grouped set: every trace is labelled normal (class 0)
  * or abnormal (class 1), and per class the traces that pass through each
  * service and each edge row are counted.  With row(i) the edge row
