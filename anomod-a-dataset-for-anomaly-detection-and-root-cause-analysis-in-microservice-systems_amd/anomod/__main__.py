@@ -30,6 +30,9 @@ def main(argv=None) -> int:
     f.add_argument("--trace-step", type=float, metavar="SECONDS",
                    help="also score per-edge time series of the spans' start times, in "
                         "windows of this many seconds")
+    f.add_argument("--trace-quantile", type=int, metavar="PCT",
+                   help="with --trace-step: also score each edge's exact per-window latency "
+                        "quantile of this percentage (0..99, e.g. 99)")
     f.add_argument("--self-time", action="store_true",
                    help="also compute the self-time (exclusive latency) edge table and "
                         "write it as \"self_edges\"")
@@ -60,7 +63,7 @@ def main(argv=None) -> int:
                             self_time=args.self_time, critical_path=args.critical_path)
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
-                     critical_path=args.critical_path)
+                     critical_path=args.critical_path, trace_quantile=args.trace_quantile)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,

@@ -86,6 +86,20 @@ class EdgeWindowsC(C.Structure):
     ]
 
 
+class EdgeWindowQuantilesC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("t0_us", C.c_uint64),
+        ("step_us", C.c_uint64),
+        ("nq", C.c_uint32),
+        ("q_pct", C.POINTER(C.c_uint32)),
+        ("count", C.POINTER(C.c_uint64)),
+        ("q_us", C.POINTER(C.c_uint32)),
+        ("outside", C.c_uint64),
+    ]
+
+
 class TraceSpectrumC(C.Structure):
     _fields_ = [
         ("n_services", C.c_uint32),
@@ -190,6 +204,7 @@ _SIGS = {
     "anomod_spans_get_start_us": (_i32, [_vp, _vp, _P(_u64)]),
     "anomod_spans_fill_start_synthetic": (_i32, [_vp, _vp, _u64, _u64, _u64]),
     "anomod_edge_windows_spans": (_i32, [_vp, _vp, _P(EdgeWindowsC)]),
+    "anomod_edge_window_quantiles_spans": (_i32, [_vp, _vp, _P(EdgeWindowQuantilesC)]),
     "anomod_decoded_start_us": (_i32, [_vp, _P(_u64)]),
     "anomod_spans_set_unique_ids": (_i32, [_vp, C.c_int]),
     "anomod_spans_unique_ids": (_i32, [_vp, _P(C.c_int)]),

@@ -437,6 +437,49 @@ class Context:
             if tmp is not None:
                 tmp.free()
 
+    def edge_window_quantiles(self, spans: DeviceSpans | SpanSet, t0_us: int, step_us: int,
+                              n_windows: int, q_pct=(50, 99), with_table: bool = True
+                              ) -> EdgeWindows:
+        """Exact per-window edge latency quantiles of a grouped set with start
+        times (anomod_edge_window_quantiles_spans): the windows and rows of
+        edge_windows; .q_us[w, row, k] = sorted(x)[int(c * q_pct[k] / 100)]
+        over the cell's c latencies (0 for an empty cell), .q_count the cell
+        counts.  with_table also fills count / errors / sum_us / max_us by
+        edge_windows (else they stay zero).  q_pct: 1..8 percentages in
+        [0, 99].  Rank-local.  A host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            if spans.start_us is None:
+                raise ValueError("span set has no start_us column")
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            if not 1 <= int(n_windows) <= 65536 or int(n_windows) * edge_rows(S) > 1 << 24:
+                raise L.AnomodError(L.EINVAL, f"n_windows={n_windows} outside [1, 65536] or "
+                                    f"n_windows * edge rows > 2^24 (n_services={S})")
+            qs = [int(q) for q in q_pct]
+            if not 1 <= len(qs) <= 8 or any(not 0 <= q <= 99 for q in qs):
+                raise L.AnomodError(L.EINVAL, f"q_pct={tuple(q_pct)}: 1..8 percentages in [0, 99]")
+            if with_table:
+                win = self.edge_windows(spans, t0_us, step_us, n_windows)
+            else:
+                win = EdgeWindows.empty(spans.services, t0_us, step_us, n_windows)
+            q = np.asarray(qs, np.uint32)
+            E = edge_rows(S)
+            win.q_pct = tuple(qs)
+            win.q_us = np.zeros((n_windows, E, len(qs)), np.uint32)
+            win.q_count = np.zeros((n_windows, E), np.uint64)
+            cs = L.EdgeWindowQuantilesC(S, n_windows, t0_us, step_us, len(qs),
+                                        L.ptr(q, C.c_uint32), L.ptr(win.q_count, C.c_uint64),
+                                        L.ptr(win.q_us, C.c_uint32), 0)
+            self._check(self._lib.anomod_edge_window_quantiles_spans(self.handle, spans.handle,
+                                                                     C.byref(cs)))
+            win.outside = int(cs.outside)
+            return win
+        finally:
+            if tmp is not None:
+                tmp.free()
+
     def self_time(self, spans: DeviceSpans | SpanSet, with_hist: bool = True,
                   per_span: bool = False):
         """Self-time (exclusive latency) edge table of a grouped set

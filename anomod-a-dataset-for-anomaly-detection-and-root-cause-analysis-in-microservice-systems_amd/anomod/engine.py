@@ -231,10 +231,12 @@ def _latency_shift(cur: EdgeTable, base: EdgeTable, min_count: int = 10) -> np.n
     return ratio.reshape(S + 2, S).max(axis=0)
 
 
-def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int) -> np.ndarray:
-    """Per-service trace anomaly score from the window scores Z [n, 2 * active
-    edges] of win.matrix(): the first score window is dropped (the EWMA
-    variance starts at 0 there), a column scores the mean of its top k =
+def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int,
+                        cols_per_edge: int = 2) -> np.ndarray:
+    """Per-service trace anomaly score from the window scores Z [n,
+    cols_per_edge * active edges] of win.matrix() (3 columns an edge with its
+    quantile column): the first score window is dropped (the EWMA variance
+    starts at 0 there), a column scores the mean of its top k =
     max(1, n_left // 20) windows, and a service takes the max over the columns
     of the edges it is the child of (row % S; ROOT and ORPHAN rows included)."""
     out = np.zeros(S)
@@ -244,7 +246,7 @@ def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int) -> np.ndarray:
     k = max(1, Z.shape[0] // 20)
     top = np.sort(Z, axis=0)[-k:].mean(axis=0)
     active = np.nonzero(win.count.sum(axis=0))[0]
-    child = np.repeat(active % S, 2)
+    child = np.repeat(active % S, int(cols_per_edge))
     np.maximum.at(out, child, top[: child.shape[0]])
     return out
 
@@ -254,7 +256,8 @@ MAX_TRACE_CELLS = 1 << 24
 
 
 def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float,
-                   min_count: int) -> tuple[EdgeWindows, np.ndarray]:
+                   min_count: int, quantile: int | None = None
+                   ) -> tuple[EdgeWindows, np.ndarray]:
     if spans.start_us is None:
         raise ValueError("features(trace_step_s=...): the span set has no start_us column")
     step_us = max(1, int(round(step_s * 1e6)))
@@ -263,12 +266,16 @@ def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: flo
     t0 = int(nz.min()) // step_us * step_us if nz.size else 0
     T = (int(nz.max()) - t0) // step_us + 1 if nz.size else 1
     T = max(1, min(T, MAX_TRACE_WINDOWS, MAX_TRACE_CELLS // max(1, edge_rows(S))))
-    win = ctx.edge_windows(spans, t0, step_us, T)
-    mm = win.matrix(min_count).pad_to_multiple(W)
+    if quantile is None:
+        win = ctx.edge_windows(spans, t0, step_us, T)
+        mm = win.matrix(min_count).pad_to_multiple(W)
+    else:
+        win = ctx.edge_window_quantiles(spans, t0, step_us, T, q_pct=(int(quantile),))
+        mm = win.matrix(min_count, quantile=int(quantile)).pad_to_multiple(W)
     if mm.S == 0 or mm.T == 0:
         return win, np.zeros(S)
     Z = ctx.ewma_z(mm.X, 2.0 / (W + 1), W, eps)
-    return win, trace_window_scores(Z, win, S)
+    return win, trace_window_scores(Z, win, S, 2 if quantile is None else 3)
 
 
 def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
@@ -276,11 +283,16 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              baseline: "Features | None" = None, trace_step_s: float | None = None,
              trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5,
              self_time: bool = False, spectrum: bool = False,
-             spectrum_rows: str = "root", critical_path: bool = False) -> Features:
+             spectrum_rows: str = "root", critical_path: bool = False,
+             trace_quantile: int | None = None) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
-    the score gains 0.25 * ts / (1 + ts).  With self_time the result also
+    the score gains 0.25 * ts / (1 + ts); trace_quantile=q (a percentage in
+    [0, 99]; needs trace_step_s) adds the exact per-window latency quantile of
+    every edge (Context.edge_window_quantiles) as a third scored series, so a
+    fault that slows a fraction of an edge's calls shows in the tail series
+    where the per-window mean dilutes it.  With self_time the result also
     holds the self-time edge table (Context.self_time), and the latency term
     against a baseline that has one is the p99 growth of self time instead of
     the inclusive duration (components["latency_kind"] says which), so a slow
@@ -296,6 +308,10 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     the critical path (latency_kind "critical", ahead of "self" and
     "inclusive"): a span that merely runs beside a longer sibling no longer
     raises it, and a fan-out parent's own work does."""
+    if trace_quantile is not None and trace_step_s is None:
+        raise ValueError("features(trace_quantile=...) needs trace_step_s")
+    if trace_quantile is not None and not 0 <= int(trace_quantile) <= 99:
+        raise ValueError(f"features(trace_quantile={trace_quantile}): a percentage in [0, 99]")
     ctx = ctx or default_context()
     edges = ctx.edge_aggregate(exp.spans, with_hist=with_hist)
     self_edges = ctx.self_time(exp.spans, with_hist=with_hist) if self_time else None
@@ -359,11 +375,14 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     if trace_step_s is None:
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
                         spectrum=spec, cp_edges=cp_edges)
-    win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count)
+    win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count,
+                             trace_quantile)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
     params["components"]["trace"] = tsq
     params.update(trace_step_s=trace_step_s, trace_W=trace_W, trace_eps=trace_eps,
                   trace_min_count=trace_min_count)
+    if trace_quantile is not None:
+        params["trace_quantile"] = int(trace_quantile)
     return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
                     spectrum=spec, cp_edges=cp_edges)

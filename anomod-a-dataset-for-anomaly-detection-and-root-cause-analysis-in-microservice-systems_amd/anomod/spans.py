@@ -259,6 +259,11 @@ class EdgeWindows:
     sum_us: np.ndarray   # u64 [T, E]
     max_us: np.ndarray   # u32 [T, E]; 0 for an empty cell
     outside: int = 0     # spans that start before t0_us or at / after the last window's end
+    # Context.edge_window_quantiles: the exact per-cell order statistics
+    # sorted(x)[int(c * q / 100)] and the cell counts they were taken over
+    q_pct: tuple | None = None
+    q_us: np.ndarray | None = None      # u32 [T, E, nq]; 0 for an empty cell
+    q_count: np.ndarray | None = None   # u64 [T, E]
 
     @property
     def n_windows(self) -> int:
@@ -271,32 +276,51 @@ class EdgeWindows:
                            np.zeros(shape, np.uint64), np.zeros(shape, np.uint64),
                            np.zeros(shape, np.uint32))
 
-    def matrix(self, min_count: int = 5):
+    def matrix(self, min_count: int = 5, quantile: int | None = None):
         """The table as a time-major series matrix for the EWMA/z kernels: the
         active edges (non-zero total count, ascending row) give two f32
         columns each, log2(1 + count) and log2(1 + sum_us / count) (NaN where
         the window holds fewer than min_count spans of the edge), computed in
         f64.  Series keys: ("edge_count" | "edge_mean_us", (("parent", name),
-        ("child", name))); timestamps are the window starts in epoch seconds."""
+        ("child", name))); timestamps are the window starts in epoch seconds.
+        With quantile=q (a percentage of q_pct: Context.edge_window_quantiles)
+        every active edge gets a third column, log2(1 + q_us) of that
+        percentage (NaN where the cell holds fewer than min_count spans), key
+        ("edge_p<q>_us", labels)."""
         from .decode import MetricMatrix
 
         S = len(self.services)
         T = self.n_windows
+        cols = 2
+        if quantile is not None:
+            if self.q_pct is None or self.q_us is None or self.q_count is None:
+                raise ValueError("matrix(quantile=...): the table holds no quantiles "
+                                 "(Context.edge_window_quantiles)")
+            if int(quantile) not in [int(q) for q in self.q_pct]:
+                raise ValueError(f"matrix(quantile={quantile}): not among q_pct={self.q_pct}")
+            kq = [int(q) for q in self.q_pct].index(int(quantile))
+            cols = 3
         active = np.nonzero(self.count.sum(axis=0))[0]
         cnt = self.count[:, active].astype(np.float64)
         tot = self.sum_us[:, active].astype(np.float64)
-        X = np.empty((T, 2 * active.shape[0]), np.float32)
-        X[:, 0::2] = np.log2(1.0 + cnt)
+        X = np.empty((T, cols * active.shape[0]), np.float32)
+        X[:, 0::cols] = np.log2(1.0 + cnt)
         with np.errstate(divide="ignore", invalid="ignore"):
             mean = np.where(self.count[:, active] >= max(int(min_count), 1),
                             np.log2(1.0 + tot / cnt), np.nan)
-        X[:, 1::2] = mean
+        X[:, 1::cols] = mean
+        if cols == 3:
+            X[:, 2::3] = np.where(self.q_count[:, active] >= max(int(min_count), 1),
+                                  np.log2(1.0 + self.q_us[:, active, kq].astype(np.float64)),
+                                  np.nan)
         series = []
         for r in active.tolist():
             p, c = divmod(r, S)
             name = "ROOT" if p == S else "ORPHAN" if p == S + 1 else self.services[p]
             labels = (("parent", name), ("child", self.services[c]))
             series += [("edge_count", labels), ("edge_mean_us", labels)]
+            if cols == 3:
+                series.append((f"edge_p{int(quantile)}_us", labels))
         ts = (self.t0_us + np.arange(T, dtype=np.float64) * self.step_us) / 1e6
         return MetricMatrix(X, ts, series)
 

@@ -1888,10 +1888,14 @@ int anomod_edge_quantiles_exact(anomod_ctx* ctx, const anomod_spans* spans, uint
     // per-span (edge, latency) keys from the aggregation kernel's own walk and
     // parent rule, then one radix sort over edge|dur
     rc = span_edge_keys(ctx, spans, S, keys, d_ctr);
+    int passes = 0;
     if (rc == ANOMOD_OK)
       e = radix_sort_u64(reinterpret_cast<const uint64_t*>(keys),
                          reinterpret_cast<uint64_t*>(sorted), n, 0, 32 + kbits, tmp, sort_tmp,
-                         ctx->stream);
+                         ctx->stream, &passes);
+    if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests, timing)
+      fprintf(stderr, "anomod: exact edge quantiles: %llu keys of %d bits, %d sort passes\n",
+              (unsigned long long)n, 32 + kbits, passes);
   }
   if (e == hipSuccess && rc == ANOMOD_OK) {
     hipLaunchKernelGGL(exact_pick_kernel, dim3((E + 255) / 256), dim3(256), 0, ctx->stream,

@@ -1,7 +1,8 @@
 // Hand-written device sort / compaction / sum primitives (CDNA4), used by the
 // cross-check and summary paths: the exact per-edge quantiles (edge_agg.hip,
-// SURVEY.md §8a a11) and the API-response value summary (summary.hip, §8f row
-// 3).  Both restate the reference's sorted(x)[int(n*q)]
+// SURVEY.md §8a a11), their per-window form (edge_window_quantiles.hip) and the
+// API-response value summary (summary.hip, §8f row 3).  All restate the
+// reference's sorted(x)[int(n*q)]
 // (SN_collection-scripts/Dataset/api_responses/monitor_http_responses.py:
 // 180-190), so they need a stable sort of 64-bit keys; no library sort.
 #pragma once

@@ -405,6 +405,38 @@ typedef struct {
 } anomod_edge_windows;
 int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               anomod_edge_windows* out);
+/* Per-window edge latency quantiles of a grouped set with a start-time
+ * column: the rows and the window rule of anomod_edge_windows_spans (a span
+ * outside [0, n_windows) is counted in `outside` and lies in no cell; a span
+ * at a position outside [trace_ptr[0], trace_ptr[n_traces]) lies in no cell
+ * and is not counted).  For cell w * E + row holding c spans with sorted
+ * latencies x[0..c):
+ *   count[cell]         = c
+ *   q_us[cell * nq + k] = x[(u64)((double)c * ((double)q_pct[k] / 100.0))]
+ * — the index rule of anomod_edge_quantiles_exact, the reference's
+ * sorted(x)[int(n*q)] — and 0 in every q_us entry of an empty cell (count
+ * tells it from a cell whose latencies are 0).  One radix sort of
+ * (cell, latency) keys: every result is an integer, bit-exact for any launch
+ * geometry.  ANOMOD_ESTATE for a set without a start column or an ungrouped
+ * set; ANOMOD_EINVAL for a service index >= S, n_windows / step_us / nq /
+ * q_pct out of range, or more than 2^32 - 4097 spans in traces; n == 0 gives
+ * zeros.  The workspace (24 B a span plus the tables) is allocated for the
+ * call and freed on return.  The call is rank-local: no collective runs even
+ * with a communicator attached (quantiles do not merge).  The set's hints
+ * are read and updated only as anomod_edge_windows_spans does.              */
+typedef struct {
+  uint32_t n_services;    /* in : S; E = (S + 2) * S as in anomod_edge_table     */
+  uint32_t n_windows;     /* in : T in [1, 65536], T * E <= 2^24, else EINVAL    */
+  uint64_t t0_us;         /* in                                                  */
+  uint64_t step_us;       /* in : >= 1                                           */
+  uint32_t nq;            /* in : 1..8                                           */
+  const uint32_t* q_pct;  /* in : [nq] host, each in [0, 99]                     */
+  uint64_t* count;        /* [T * E] host, may be NULL                           */
+  uint32_t* q_us;         /* [T * E * nq] host, cell-major; 0 for an empty cell  */
+  uint64_t outside;       /* out                                                 */
+} anomod_edge_window_quantiles;
+int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                                       anomod_edge_window_quantiles* out);
 /* Self-time (exclusive latency) edge table of a grouped set.  The parent of
  * span i is the first span of its trace, in position order, whose span_id
  * equals i's parent_span_id — the edge table's rule, duplicated ids
