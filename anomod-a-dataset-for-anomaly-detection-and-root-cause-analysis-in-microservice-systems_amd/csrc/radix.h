@@ -21,8 +21,11 @@ size_t radix_temp_bytes(uint64_t n);
 // and scatter bases are u32): larger n returns hipErrorInvalidValue.
 constexpr uint64_t kMaxSortKeys = 0xFFFFFFFFull - 4096;
 
-// Stable LSD radix sort of n u64 keys by bits [begin_bit, end_bit) (keys must
-// be < 2^end_bit), 8-bit digits: per pass the digit counts of every
+// Stable LSD radix sort of n u64 keys by bits [begin_bit, end_bit) (bits below
+// begin_bit and at or above end_bit may hold anything: they do not affect the
+// order, so keys equal in the sorted bits keep their input order; begin_bit ==
+// end_bit returns the input), 8-bit digits, the last one end_bit - s bits wide
+// when fewer than 8 remain: per pass the digit counts of every
 // 4096-key tile, their exclusive scan over tiles, one scatter (wave-ballot
 // ranks, the tile staged in LDS in digit order, written as coalesced digit
 // runs).  A pass whose digit is the same in every key (from one OR / AND
