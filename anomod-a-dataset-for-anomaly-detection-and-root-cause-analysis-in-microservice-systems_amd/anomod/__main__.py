@@ -1,5 +1,5 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
-                                 [--spectrum] [--critical-path]
+                                 [--spectrum] [--critical-path] [--shapes]
                                  [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
@@ -17,6 +17,27 @@ import json
 import sys
 
 from . import features, load_experiment, rank
+
+
+def shapes_doc(census, spans, base=None, top: int = 20) -> dict:
+    """The "shapes" object of the features JSON: distinct count, off-tree
+    spans and the top shapes (hex fingerprint, count, abnormal, exemplar trace
+    with its span count and services, and `new` against the baseline census:
+    None without one)."""
+    k = min(top, int(census.shape.shape[0]))
+    new = census.novel(base)[:k].tolist() if base is not None else [None] * k
+    holds = census.service_sets(spans)[:k]
+    ptr = spans.trace_ptr
+    rows = []
+    for i in range(k):
+        t = int(census.first_trace[i])
+        rows.append({"shape": f"{int(census.shape[i]):016x}", "count": int(census.count[i]),
+                     "abnormal": int(census.abnormal[i]), "exemplar_trace": t,
+                     "exemplar_spans": int(ptr[t + 1]) - int(ptr[t]),
+                     "services": [s for s, h in zip(census.services, holds[i]) if h],
+                     "new": new[i]})
+    return {"distinct": int(census.n_shapes), "off_tree_spans": int(census.off_tree_spans),
+            "top": rows}
 
 
 def main(argv=None) -> int:
@@ -43,6 +64,10 @@ def main(argv=None) -> int:
                    help="also compute the critical-path edge table (the spans that determined "
                         "each trace's end-to-end latency and the exclusive time each added; "
                         "needs span start times) and write it as \"cp_edges\"")
+    f.add_argument("--shapes", action="store_true",
+                   help="also take the trace shape census (the distinct call trees of the run "
+                        "and how many traces have each; against --baseline, which shapes are "
+                        "new) and write it as \"shapes\"")
     f.add_argument("--baseline", metavar="TRACES",
                    help="trace file (or dir) of a normal run: its features are the baseline "
                         "of the latency term and of the spectrum's latency thresholds")
@@ -60,10 +85,12 @@ def main(argv=None) -> int:
     baseline = None
     if args.baseline:
         baseline = features(load_experiment(args.baseline), W=args.window,
-                            self_time=args.self_time, critical_path=args.critical_path)
+                            self_time=args.self_time, critical_path=args.critical_path,
+                            shapes=args.shapes)
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
-                     critical_path=args.critical_path, trace_quantile=args.trace_quantile)
+                     critical_path=args.critical_path, trace_quantile=args.trace_quantile,
+                     shapes=args.shapes)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -94,6 +121,9 @@ def main(argv=None) -> int:
                                for i, s in enumerate(names)},
             "ochiai": dict(zip(names, map(float, sp.ochiai()))),
         }
+    if feats.shapes is not None:
+        doc["shapes"] = shapes_doc(feats.shapes, exp.spans,
+                                   baseline.shapes if baseline is not None else None)
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

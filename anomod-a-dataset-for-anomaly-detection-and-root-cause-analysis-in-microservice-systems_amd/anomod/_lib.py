@@ -113,6 +113,24 @@ class TraceSpectrumC(C.Structure):
     ]
 
 
+class TraceShapesC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("use_errors", C.c_uint32),
+        ("svc_key", C.POINTER(C.c_uint64)),
+        ("trace_class", C.POINTER(C.c_uint8)),
+        ("cap", C.c_uint64),
+        ("n_shapes", C.c_uint64),
+        ("off_tree_spans", C.c_uint64),
+        ("shape", C.POINTER(C.c_uint64)),
+        ("count", C.POINTER(C.c_uint64)),
+        ("abnormal", C.POINTER(C.c_uint64)),
+        ("first_trace", C.POINTER(C.c_uint64)),
+        ("trace_shape", C.POINTER(C.c_uint64)),
+        ("path_hash", C.POINTER(C.c_uint64)),
+    ]
+
+
 class TraceStructC(C.Structure):
     _fields_ = [
         ("n_services", C.c_uint32),
@@ -230,6 +248,7 @@ _SIGS = {
     "anomod_edge_critical_path_spans": (_i32, [_vp, _vp, _u32, _P(EdgeTableC), _P(C.c_uint32),
                                                _P(C.c_uint8)]),
     "anomod_trace_spectrum_spans": (_i32, [_vp, _vp, _P(TraceSpectrumC)]),
+    "anomod_trace_shapes_spans": (_i32, [_vp, _vp, _P(TraceShapesC)]),
     "anomod_edge_aggregate_host": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _u32, _i32,
                                           _P(_i32), _P(_i32), _P(EdgeTableC)]),
     "anomod_edge_aggregate": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _P(EdgeTableC)]),

@@ -11,8 +11,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import (CriticalPath, EdgeTable, EdgeWindows, SpanSet, TraceSpectrum, TraceStructure,
-                    edge_rows)
+from .spans import (CriticalPath, EdgeTable, EdgeWindows, SpanSet, TraceShapes, TraceSpectrum,
+                    TraceStructure, edge_rows)
 
 
 @dataclass
@@ -568,6 +568,65 @@ class Context:
                                                               C.byref(cs)))
             sp.n_traces[:] = (cs.n_traces[0], cs.n_traces[1])
             return sp
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def trace_shapes(self, spans: DeviceSpans | SpanSet, trace_class=None,
+                     use_errors: bool = False, cap: int | None = None, per_trace: bool = False,
+                     per_span: bool = False, svc_key="names") -> TraceShapes:
+        """Shape census of a grouped set (anomod_trace_shapes_spans): the
+        distinct trace shapes — fingerprints of the multiset of labelled
+        root-to-span call paths — with their counts, by count descending.
+        trace_class: u8 [n_traces] (e.g. TraceSpectrum.trace_abnormal) splits
+        the counts into .abnormal.  use_errors makes the error flag part of a
+        span's label.  cap: the most shapes to return (None: all — a second
+        call follows when the set has more than 65,536).  svc_key: "names" keys the services by the hash of
+        their names (decode.hash64), so shapes compare across runs with
+        different service lists; None keys them by index.
+        per_trace / per_span also return trace_shape / path_hash.  Rank-local.
+        A host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            nt, n = int(spans.n_traces), int(spans.n_spans)
+            keys = None
+            if svc_key is not None:
+                if svc_key != "names":
+                    raise ValueError(f"svc_key={svc_key!r}: 'names' or None")
+                from .decode import hash64
+                keys = np.array([hash64(s) for s in spans.services], np.uint64)
+            cls = None
+            if trace_class is not None:
+                cls = np.ascontiguousarray(trace_class, np.uint8)
+                if cls.shape != (nt,):
+                    raise ValueError(f"trace_class has shape {cls.shape}, expected ({nt},)")
+            tshape = np.zeros(nt, np.uint64) if per_trace else None
+            phash = np.zeros(n, np.uint64) if per_span else None
+
+            def call(m, with_cols):
+                arrs = [np.zeros(m, np.uint64) for _ in range(4)]
+                cs = L.TraceShapesC(S, 1 if use_errors else 0, L.ptr(keys, C.c_uint64),
+                                    L.ptr(cls, C.c_uint8), m, 0, 0,
+                                    *(L.ptr(a if m else None, C.c_uint64) for a in arrs),
+                                    L.ptr(tshape if with_cols else None, C.c_uint64),
+                                    L.ptr(phash if with_cols else None, C.c_uint64))
+                self._check(self._lib.anomod_trace_shapes_spans(self.handle, spans.handle,
+                                                                C.byref(cs)))
+                return cs, arrs
+
+            if cap is not None and int(cap) < 0:
+                raise ValueError(f"cap={cap}: a count of shapes")
+            m = min(nt, 1 << 16) if cap is None else int(cap)
+            cs, arrs = call(m, True)
+            if cap is None and int(cs.n_shapes) > m:
+                m = int(cs.n_shapes)
+                cs, arrs = call(m, True)
+            k = min(m, int(cs.n_shapes))
+            return TraceShapes(list(spans.services), *(a[:k] for a in arrs), int(cs.n_shapes),
+                               int(cs.off_tree_spans), tshape, phash, bool(use_errors))
         finally:
             if tmp is not None:
                 tmp.free()

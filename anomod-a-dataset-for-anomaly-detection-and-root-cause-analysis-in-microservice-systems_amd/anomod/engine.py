@@ -23,7 +23,8 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import EdgeTable, EdgeWindows, SpanSet, TraceSpectrum, edge_rows, spectrum_thresholds
+from .spans import (EdgeTable, EdgeWindows, SpanSet, TraceShapes, TraceSpectrum, edge_rows,
+                    spectrum_thresholds)
 
 # --------------------------------------------------------------------------
 # Ground-truth labels (experiment name -> faulty service), SURVEY.md §2:
@@ -171,6 +172,8 @@ class Features:
     spectrum: TraceSpectrum | None = None
     # features(critical_path=True): the critical-path edge table
     cp_edges: EdgeTable | None = None
+    # features(shapes=True): the trace shape census
+    shapes: TraceShapes | None = None
 
 
 _default_ctx: Context | None = None
@@ -284,7 +287,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5,
              self_time: bool = False, spectrum: bool = False,
              spectrum_rows: str = "root", critical_path: bool = False,
-             trace_quantile: int | None = None) -> Features:
+             trace_quantile: int | None = None, shapes: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -307,7 +310,13 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     that has one the latency term is the p99 growth of the time spans add on
     the critical path (latency_kind "critical", ahead of "self" and
     "inclusive"): a span that merely runs beside a longer sibling no longer
-    raises it, and a fan-out parent's own work does."""
+    raises it, and a fan-out parent's own work does.  With shapes the result
+    also holds the trace shape census (Context.trace_shapes, service keys by
+    name; the counts are split by the spectrum's trace labels when spectrum
+    is on), and against a baseline that has one the score gains 0.25 * the
+    shape novelty (TraceShapes.novelty: per service, the share of the traces
+    — among those whose shape's exemplar holds the service — whose shape the
+    baseline run does not have; components["shape_novelty"])."""
     if trace_quantile is not None and trace_step_s is None:
         raise ValueError("features(trace_quantile=...) needs trace_step_s")
     if trace_quantile is not None and not 0 <= int(trace_quantile) <= 99:
@@ -372,9 +381,17 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         params["components"]["spectrum"] = och
         params["components"]["spectrum_thresholds"] = "baseline" if thr is not None else "errors-only"
         score = score + 0.25 * och
+    census = None
+    if shapes:
+        census = ctx.trace_shapes(exp.spans,
+                                  trace_class=spec.trace_abnormal if spec is not None else None)
+        if baseline is not None and baseline.shapes is not None:
+            nov = census.novelty(exp.spans, baseline.shapes)
+            params["components"]["shape_novelty"] = nov
+            score = score + 0.25 * nov
     if trace_step_s is None:
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
-                        spectrum=spec, cp_edges=cp_edges)
+                        spectrum=spec, cp_edges=cp_edges, shapes=census)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count,
                              trace_quantile)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
@@ -385,7 +402,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         params["trace_quantile"] = int(trace_quantile)
     return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
-                    spectrum=spec, cp_edges=cp_edges)
+                    spectrum=spec, cp_edges=cp_edges, shapes=census)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

@@ -382,6 +382,58 @@ class TraceSpectrum:
         return _ochiai(self.edge_traces[1], self.edge_traces[0], int(self.n_traces[1]))
 
 
+@dataclass
+class TraceShapes:
+    """Shape census of a span set (anomod_trace_shapes_spans): the distinct
+    trace shapes — 64-bit fingerprints of the multiset of labelled
+    root-to-span call paths of a trace — by count descending, then value
+    ascending.  The arrays hold the first min(cap, n_shapes) shapes."""
+
+    services: list[str]
+    shape: np.ndarray                 # u64 [m] the fingerprints
+    count: np.ndarray                 # u64 [m] traces with the shape
+    abnormal: np.ndarray              # u64 [m] those with trace_class != 0
+    first_trace: np.ndarray           # u64 [m] smallest trace index with the shape
+    n_shapes: int                     # distinct shapes of the set
+    off_tree_spans: int               # spans whose parent chain reaches no head
+    trace_shape: np.ndarray | None = None  # u64 [n_traces] (per_trace=True)
+    path_hash: np.ndarray | None = None    # u64 [n_spans] (per_span=True)
+    use_errors: bool = False
+
+    @property
+    def truncated(self) -> bool:
+        """The census holds fewer shapes than the set has (cap < n_shapes)."""
+        return int(self.shape.shape[0]) < int(self.n_shapes)
+
+    def novel(self, baseline: "TraceShapes") -> np.ndarray:
+        """Mask of the shapes absent from baseline.shape.  A truncated
+        baseline cannot say that a shape is absent: ValueError."""
+        if baseline.truncated:
+            raise ValueError("the baseline census is truncated "
+                             f"({baseline.shape.shape[0]} of {baseline.n_shapes} shapes)")
+        return ~np.isin(self.shape, baseline.shape)
+
+    def service_sets(self, spans: SpanSet) -> np.ndarray:
+        """bool [m, S]: the services of each shape's exemplar trace
+        (first_trace), over all spans of that trace."""
+        S = len(self.services)
+        out = np.zeros((self.shape.shape[0], S), bool)
+        ptr = spans.trace_ptr
+        for k, t in enumerate(self.first_trace.tolist()):
+            out[k, spans.svc[int(ptr[t]):int(ptr[t + 1])]] = True
+        return out
+
+    def novelty(self, spans: SpanSet, baseline: "TraceShapes") -> np.ndarray:
+        """Per service s: the traces of novel shapes whose exemplar holds s
+        over the traces of all shapes whose exemplar holds s (0 where no
+        exemplar holds s)."""
+        holds = self.service_sets(spans).astype(np.float64)
+        cnt = self.count.astype(np.float64)
+        num = (cnt * self.novel(baseline)) @ holds
+        den = cnt @ holds
+        return np.divide(num, den, out=np.zeros(holds.shape[1]), where=den > 0)
+
+
 def spectrum_thresholds(base: EdgeTable, services: list[str], *, rows: str = "root",
                         min_count: int = 10) -> np.ndarray:
     """Latency thresholds (u32 [E] over `services`) for Context.trace_spectrum

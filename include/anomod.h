@@ -518,6 +518,56 @@ typedef struct {
 } anomod_trace_spectrum;
 int anomod_trace_spectrum_spans(anomod_ctx* ctx, const anomod_spans* spans,
                                 anomod_trace_spectrum* out);
+/* Trace shape census of a grouped set: a structural fingerprint per trace,
+ * the distinct fingerprints of the set and how many traces have each.  All
+ * arithmetic is on u64, mod 2^64; mix64 is the SplitMix64 finaliser.  With
+ * par(i) the parent rule of the self-time call, a span without a parent is a
+ * head of kind ROOT (reference 0), ORPHAN (the reference names no span of the
+ * trace) or SELF (the first match is the span itself).  With the label key
+ *   K(i) = svc_key[svc(i)]
+ *          ^ (use_errors && (flags[i] & ANOMOD_FLAG_ERROR) ? 0xD1B54A32D192ED03 : 0)
+ * (svc_key == NULL stands for svc_key[s] = mix64(s + 1)) and B =
+ * 0x9E3779B97F4A7C15, the call-path hash is
+ *   P(i) = seed(kind) * B + K(i)   for a head (seeds: ROOT 0x243F6A8885A308D3,
+ *          ORPHAN 0x13198A2E03707344, SELF 0xA4093822299F31D0)
+ *   P(i) = P(par(i)) * B + K(i)    otherwise.
+ * A span whose parent chain never reaches a head (a reference cycle, or a
+ * span hanging off one) is off the tree: path_hash 0, in no shape, counted in
+ * off_tree_spans.  trace_shape[t] is the sum of mix64(P(i)) over the on-tree
+ * spans of trace t (0 for a trace with none): the multiset of labelled
+ * root-to-span call paths.  It ignores span order — with unique ids it is
+ * invariant under any permutation of the spans inside a trace — and equates
+ * trees that differ only in how equal-label siblings share their children;
+ * it separates trees that differ in any call path, as far as a 64-bit hash
+ * without an adversarial guarantee does.  The census lists the distinct
+ * trace_shape values by count descending, then value ascending: per shape its
+ * count, the traces with trace_class[t] != 0 (abnormal) and the smallest
+ * trace index (first_trace).  Bit-exact for any launch geometry.  NULL
+ * outputs are skipped; cap == 0 with NULL arrays is a size query (n_shapes);
+ * a set without traces gives n_shapes 0, a set of only empty traces one
+ * shape, 0.  Spans outside every trace read path_hash 0 and are not counted.
+ * An ungrouped set is ANOMOD_ESTATE; a service index >= n_services is
+ * ANOMOD_EINVAL; at most 2^32 - 2 spans and 2^32 - 4097 traces per call.  The
+ * call is rank-local: no collective runs even with a communicator attached.
+ * The set's histogram-form hint is neither read nor changed; an unknown order
+ * hint is probed as in the self-time call.                                  */
+typedef struct {
+  uint32_t n_services;        /* in : S                                              */
+  uint32_t use_errors;        /* in : non-zero: the error flag is part of the label  */
+  const uint64_t* svc_key;    /* in : [S] host, or NULL (mix64(s + 1))               */
+  const uint8_t* trace_class; /* in : [n_traces] host, or NULL (every trace class 0) */
+  uint64_t cap;               /* in : shapes the four arrays below hold              */
+  uint64_t n_shapes;          /* out: distinct shapes of the set                     */
+  uint64_t off_tree_spans;    /* out                                                 */
+  uint64_t* shape;            /* [cap] first min(cap, n_shapes) in census order      */
+  uint64_t* count;            /* [cap]                                               */
+  uint64_t* abnormal;         /* [cap]                                               */
+  uint64_t* first_trace;      /* [cap]                                               */
+  uint64_t* trace_shape;      /* [n_traces] host, may be NULL                        */
+  uint64_t* path_hash;        /* [n_spans] host, may be NULL                         */
+} anomod_trace_shapes;
+int anomod_trace_shapes_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                              anomod_trace_shapes* out);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
