@@ -16,9 +16,9 @@
 //   cp_us[i]    = dur_us[i] - sum of (b - a) over the selected children of i
 //                 for i on the path, else 0
 //
-// One chunk walk (chunk.h, as self_time.hip: persistent waves, <= 256 spans /
-// <= 64 whole traces per chunk, buffer loads, the columns of chunk c+1 in
-// flight while chunk c is resolved) finds every span's parent position in the
+// One chunk walk (walk.h: persistent waves, <= 256 spans / <= 64 whole traces
+// per chunk, buffer loads, the columns of chunk c+1 in flight while chunk c is
+// resolved) finds every span's parent position in the
 // wave's LDS, runs the selection of all parents of the chunk in rounds (one
 // step of every parent per round: ds_max_u64 on the parent's slot, ds_min on
 // the position among the holders of the maximum), then 8 rounds of pointer
@@ -32,8 +32,8 @@
 #include <algorithm>
 #include <cstring>
 
-#include "chunk.h"
 #include "common.h"
+#include "walk.h"
 
 namespace anomod {
 namespace {
@@ -41,10 +41,6 @@ namespace {
 using namespace chunk;
 constexpr int kCpWaves = 4;
 constexpr int kCpThreads = kCpWaves * kWave;
-// The scan dispatch of the edge kernels and of self_time.hip.
-constexpr uint32_t kNarrowRows = 512;
-enum Scan { kScanFwd = 0, kScanBidir = 1, kScanSplit = 2 };
-constexpr uint32_t kSplitFwd = 12, kSplitBwd = 4;
 
 // Per-wave LDS (every offset a multiple of 16).  Three arrays are reused once
 // the parents are found and a / b sit in registers: the ids become the u64
@@ -59,7 +55,6 @@ constexpr int kCFlag = kCSvc + kStage * 2;    // u8 trace-start flags [kStage]
 constexpr int kCBytes = kCFlag + kStage;
 static_assert(kCBytes % 16 == 0, "wave staging must stay 16-B aligned");
 
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 // span states of the selection
 constexpr uint32_t kOut = 0, kCand = 1, kOffer = 2, kSel = 3;
 // chunk jump word: ancestor position | kOk (every span up to it selected) | kDone (it is a head)
@@ -116,40 +111,10 @@ __device__ __forceinline__ void load_regs(const uint64_t* __restrict__ span_id,
   }
 }
 
-// First span of [a, b) whose id equals pid (-1: none): the forward scan of
-// sets not declared unique (self_time.hip find_first).
-constexpr uint32_t kFwdScan = 10;
-static_assert(kFwdScan % 2 == 0 && kFwdScan <= kScanSlack, "scan step");
-__device__ __forceinline__ int find_first(const uint64_t* lsid, uint32_t a, uint32_t b,
-                                          uint64_t pid) {
-  for (uint32_t q0 = a; q0 < b; q0 += kFwdScan) {
-    uint64_t v[kFwdScan];
-#pragma unroll
-    for (uint32_t j = 0; j < kFwdScan; ++j) v[j] = lsid[q0 + j];
-    uint32_t m = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kFwdScan; ++j) m |= (v[j] == pid ? 1u : 0u) << j;
-    const uint32_t hi = (b - q0) < kFwdScan ? (b - q0) : kFwdScan;  // >= 1
-    m &= (1u << hi) - 1u;
-    if (m) return (int)(q0 + __ffs(m) - 1u);
-  }
-  return -1;
-}
-
 __device__ __forceinline__ uint64_t sat_end(uint64_t s, uint32_t d) {
   const uint64_t e = s + (uint64_t)d;
   return e < s ? ~0ull : e;
 }
-
-__device__ __forceinline__ unsigned long long make_rec(uint32_t row, uint32_t S, uint32_t sf,
-                                                       uint32_t v) {
-  return ((unsigned long long)(row * S + (sf & 0xFFFFu)) << 33) |
-         ((unsigned long long)((sf >> 16) & ANOMOD_FLAG_ERROR ? 1u : 0u) << 32) | v;
-}
-
-// The record of a span off the path: edge_aggregate_records skips it (no real
-// record is all ones: a row index stays far below 2^31).
-constexpr unsigned long long kSkipRec = ~0ull;
 
 template <int SCAN>
 __device__ __forceinline__ void cp_chunk(unsigned char* wsm, int lane, const Chunk& c,
@@ -196,12 +161,7 @@ __device__ __forceinline__ void cp_chunk(unsigned char* wsm, int lane, const Chu
       p = a.S + 1u;  // ORPHAN unless found in the trace
       uint32_t ta, tb;
       trace_bounds(Sm, r, lane, c.n, ta, tb);
-      if constexpr (SCAN == kScanSplit)
-        q = find_parent_split<kSplitFwd, kSplitBwd>(llo, lhi, ta, tb, i, R.pid[r]);
-      else if constexpr (SCAN == kScanBidir)
-        q = find_parent_bidir<kFwd, kBwd>(lsid, ta, tb, i, R.pid[r]);
-      else
-        q = find_first(lsid, ta, tb, R.pid[r]);
+      q = find_parent<SCAN>(lsid, llo, lhi, ta, tb, i, R.pid[r]);
       if (q >= 0) p = lsvc[q];  // a self-reference keeps its own service as parent
     }
     row[r] = p;
@@ -316,7 +276,7 @@ __device__ __forceinline__ void cp_chunk(unsigned char* wsm, int lane, const Chu
     const bool on = i < c.n && (w[r] & (kOk | kDone)) == (kOk | kDone);
     const uint32_t cp = on ? R.dur[r] - lsum[i] : 0u;
     if (i >= c.n) continue;
-    a.rec[c.base + i] = on ? make_rec(row[r], a.S, R.sf[r], cp) : kSkipRec;
+    a.rec[c.base + i] = on ? edge_rec(row[r], a.S, R.sf[r], cp) : kSkipRec;
     if (a.cp_us) a.cp_us[c.base + i] = cp;
     if (a.on_path) a.on_path[c.base + i] = on ? 1 : 0;
   }
@@ -333,95 +293,24 @@ __global__ __launch_bounds__(kCpThreads, 3) void critical_path_kernel(
     CpArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kCBytes * kCpWaves];
   const int lane = threadIdx.x & (kWave - 1);
-  const int wid = threadIdx.x / kWave;
-  unsigned char* wsm = smem + wid * kCBytes;
-  const uint64_t gw = (uint64_t)blockIdx.x * kCpWaves + wid;
-  const uint64_t nw = (uint64_t)gridDim.x * kCpWaves;
-  auto run = [&](const uint64_t t_begin, const uint64_t t_end) __attribute__((always_inline)) {
-    // Software pipeline (as the edge kernel): the bounds of chunk c+2 and the
-    // span columns of chunk c+1 are in flight while chunk c is resolved.
-    uint64_t lo, hi;
-    load_bounds(trace_ptr, t_begin, t_end, lane, lo, hi);
-    Chunk cur = make_chunk(t_begin, t_end, lane, lo, hi);
-    uint64_t t_cur = t_begin;
-    Regs R;
-    load_regs(span_id, parent, svcfl, dur, start, cur, lane, R);
-    uint64_t t_next = t_begin + (cur.k ? cur.k : 1u);
-    load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-    while (true) {
-      const bool has_next = t_next < t_end;
-      const uint64_t t_nxt = t_next;
-      Chunk nxt{};
-      Regs Rn;
-      if (has_next) {
-        nxt = make_chunk(t_next, t_end, lane, lo, hi);
-        load_regs(span_id, parent, svcfl, dur, start, nxt, lane, Rn);
-        t_next += nxt.k ? nxt.k : 1u;
-        load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-      }
-      if (cur.k == 0) {  // longer than kStage: listed for critical_path_big_kernel
-        if (lane == 0) {
-          const unsigned long long j = atomicAdd(&a.big[0], 1ull);
-          if (j < a.big_cap) {  // (always: the list is sized to the counted long traces)
-            a.big_list[2 * j] = t_cur;
-            a.big_list[2 * j + 1] = atomicAdd(&a.big[1], (unsigned long long)cur.n);
-          }
-        }
-      } else {
-        cp_chunk<SCAN>(wsm, lane, cur, R, a);
-      }
-      if (!has_next) break;
-      cur = nxt;
-      t_cur = t_nxt;
-      R = Rn;
-    }
-  };
-  // As the edge kernel: a static share per wave, then the last 1 / kDyn of
-  // the traces in segments of kDynSeg from a global counter.
-  constexpr uint64_t kDyn = 4, kDynSeg = 512;
-  const uint64_t n_static = n_traces - n_traces / kDyn;
-  uint64_t t_begin = uniform64(n_static * gw / nw);
-  uint64_t t_end = uniform64(n_static * (gw + 1) / nw);
-  while (true) {
-    if (t_begin < t_end) run(t_begin, t_end);
-    if (n_static == n_traces) break;
-    unsigned long long g = 0;
-    if (lane == 0) g = atomicAdd(a.ctr, (unsigned long long)kDynSeg);
-    g = __shfl(g, 0);
-    t_begin = uniform64(n_static + g);
-    if (t_begin >= n_traces) break;
-    t_end = uniform64(t_begin + kDynSeg < n_traces ? t_begin + kDynSeg : n_traces);
-  }
+  unsigned char* wsm = smem + (threadIdx.x / kWave) * kCBytes;
+  walk_traces<kCpWaves, 4, Regs>(
+      trace_ptr, n_traces, a.ctr,
+      [&](const Chunk& c, Regs& R) __attribute__((always_inline)) {
+        load_regs(span_id, parent, svcfl, dur, start, c, lane, R);
+      },
+      [&](const Chunk& c, uint32_t, uint64_t, const Regs& R) __attribute__((always_inline)) {
+        cp_chunk<SCAN>(wsm, lane, c, R, a);
+      },
+      // longer than kStage: listed for critical_path_big_kernel
+      [&](uint64_t t, uint32_t n) __attribute__((always_inline)) {
+        list_long(a.big, a.big_list, a.big_cap, lane, t, n);
+      });
 }
 
 // ---- long traces ----------------------------------------------------------
-// Traces and spans of the set that outgrow a chunk: cnt[0] traces, cnt[1]
-// spans (sizes the list and the per-span scratch before the walk).
-__global__ __launch_bounds__(256) void cp_long_count_kernel(const uint64_t* __restrict__ trace_ptr,
-                                                            uint64_t n_traces,
-                                                            unsigned long long* __restrict__ cnt) {
-  unsigned long long nt = 0, ns = 0;
-  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n_traces;
-       t += (uint64_t)gridDim.x * 256) {
-    const uint64_t L = trace_ptr[t + 1] - trace_ptr[t];
-    if (L > (uint64_t)kStage) {
-      nt += 1;
-      ns += L;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    nt += __shfl_xor(nt, o);
-    ns += __shfl_xor(ns, o);
-  }
-  if ((threadIdx.x & 63) == 0 && nt) {
-    atomicAdd(&cnt[0], nt);
-    atomicAdd(&cnt[1], ns);
-  }
-}
-
-// One workgroup per listed trace (tickets, as self_big_kernel).  Parent
-// positions come from that kernel's windowed LDS id table (id -> first
-// position in a window of kBigWin ids, windows probed in trace order).  The
+// One workgroup per listed trace (tickets).  Parent positions come from
+// walk.h's windowed LDS id table (big_parents).  The
 // per-span state lives in global scratch: a span's words are written by the
 // thread that owns the span (position % kBigThreads) or, for the words of a
 // parent, by atomics and agent-scope stores of its children; every word
@@ -434,51 +323,17 @@ __global__ __launch_bounds__(256) void cp_long_count_kernel(const uint64_t* __re
 // between the two jump buffers: O((rounds + log L) * L) global accesses for a
 // trace of L spans, rounds = the largest number of selected children of one
 // span.
-constexpr int kBigThreads = 512;
-constexpr int kBigPer = 8;
-constexpr uint32_t kBigWin = 2048;
-constexpr uint32_t kBigSlots = 2 * kBigWin;  // load <= 1/2
-static_assert((kBigSlots & (kBigSlots - 1)) == 0, "power-of-two table");
-
-__device__ __forceinline__ uint32_t big_slot(uint64_t id) {
-  return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32) & (kBigSlots - 1u);
-}
-
-template <typename T>
-__device__ __forceinline__ T aload(const T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ __forceinline__ void astore(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// Every store and atomic of the sweep has reached L2 before any thread starts
-// the next one: each wave waits for its own vector-memory operations, then the
-// workgroup's barrier (which alone waits for LDS only).  The words threads
-// share are written by agent-scope stores and atomics and read by agent-scope
-// loads, all served by L2, so no cache needs writing back or invalidating: a
-// __threadfence() per sweep made this kernel 16 times slower.
-constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0), expcnt and lgkmcnt at their maxima
-__device__ __forceinline__ void wait_stores() { __builtin_amdgcn_s_waitcnt(kWaitVm0); }
-__device__ __forceinline__ void sweep_sync() {
-  wait_stores();
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(kBigThreads) void critical_path_big_kernel(
     const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
     const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
     const uint64_t* __restrict__ start, const uint64_t* __restrict__ trace_ptr, CpArgs a) {
-  __shared__ unsigned long long bkey[kBigSlots];  // 0 = empty (id 0 is never a parent reference)
-  __shared__ uint32_t bpos[kBigSlots];            // first position in the window
+  __shared__ unsigned long long bkey[kBigSlots];
+  __shared__ uint32_t bpos[kBigSlots];
   __shared__ unsigned long long s_j;
   const int tid = threadIdx.x;
   const uint64_t nbig = a.big[0] < a.big_cap ? a.big[0] : a.big_cap;
   const uint32_t S = a.S;
-  for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-    bkey[k] = 0ull;
-    bpos[k] = kNone;
-  }
+  big_clear(bkey, bpos, tid);
   while (true) {
     __syncthreads();
     if (tid == 0) s_j = atomicAdd(&a.big[2], 1ull);
@@ -499,53 +354,11 @@ __global__ __launch_bounds__(kBigThreads) void critical_path_big_kernel(
     uint32_t* st = a.l_st + off;
     unsigned long long* jA = a.l_j[0] + off;
     unsigned long long* jB = a.l_j[1] + off;
-    // ---- parent positions (self_big_kernel's windows)
+    // ---- parent positions
     for (uint64_t b0 = 0; b0 < L; b0 += kBigThreads * kBigPer) {
       uint64_t pid[kBigPer];
-      uint32_t pp[kBigPer];  // parent position in the trace (kNone: not found yet)
-      bool need = false;
-#pragma unroll
-      for (int r = 0; r < kBigPer; ++r) {
-        const uint64_t i = b0 + (uint64_t)r * kBigThreads + tid;
-        pid[r] = i < L ? parent[lo + i] : 0ull;
-        pp[r] = kNone;
-        need |= pid[r] != 0ull;
-      }
-      for (uint32_t w0 = 0; w0 < L; w0 += kBigWin) {
-        if (!__syncthreads_or(need)) break;  // also orders the previous clear
-        for (uint32_t k = tid; k < kBigWin && (uint64_t)w0 + k < L; k += kBigThreads) {
-          const uint64_t id = span_id[lo + w0 + k];
-          if (id == 0ull) continue;
-          for (uint32_t sl = big_slot(id);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-            const unsigned long long prev = atomicCAS(&bkey[sl], 0ull, (unsigned long long)id);
-            if (prev == 0ull || prev == id) {
-              atomicMin(&bpos[sl], k);  // the first position wins
-              break;
-            }
-          }
-        }
-        __syncthreads();
-        need = false;
-#pragma unroll
-        for (int r = 0; r < kBigPer; ++r) {
-          if (pid[r] == 0ull || pp[r] != kNone) continue;
-          for (uint32_t sl = big_slot(pid[r]);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-            const unsigned long long key = bkey[sl];
-            if (key == pid[r]) {
-              pp[r] = w0 + bpos[sl];
-              break;
-            }
-            if (key == 0ull) break;
-          }
-          need |= pp[r] == kNone;
-        }
-        __syncthreads();
-        for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-          bkey[k] = 0ull;
-          bpos[k] = kNone;
-        }
-        if ((uint64_t)w0 + kBigWin >= L) break;  // (w0 += kBigWin must not wrap)
-      }
+      uint32_t pp[kBigPer];  // parent position in the trace (kNone: none)
+      big_parents(span_id, parent, lo, L, b0, tid, bkey, bpos, pid, pp);
       // The span's interval clipped to its parent's, and the span's own slots.
 #pragma unroll
       for (int r = 0; r < kBigPer; ++r) {
@@ -648,7 +461,7 @@ __global__ __launch_bounds__(kBigThreads) void critical_path_big_kernel(
       const uint32_t p = parent[lo + i] == 0ull ? S
                          : q == kNone           ? S + 1u
                                                 : (svcfl[lo + q] & 0xFFFFu);
-      a.rec[lo + i] = on ? make_rec(p, S, svcfl[lo + i], cp) : kSkipRec;
+      a.rec[lo + i] = on ? edge_rec(p, S, svcfl[lo + i], cp) : kSkipRec;
     }
   }
 }
@@ -692,112 +505,60 @@ int anomod_edge_critical_path_spans(anomod_ctx* ctx, const anomod_spans* spans, 
   if (int rc = comm_agree(ctx, local)) return rc;
 
   const uint64_t n = spans->n_spans, nt = spans->n_traces;
-  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
-  // the spans that lie in traces: [trace_ptr[0], trace_ptr[n_traces]) (spans
-  // outside every trace are on no path: their cp_us and on_path read 0)
-  uint64_t in_traces[2] = {0, 0};
-  if (nt && n) {
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces + 1, spans->trace_ptr + nt, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (!(in_traces[0] <= in_traces[1] && in_traces[1] <= n)) {
-      set_error(ctx, "trace_ptr range [%llu, %llu) outside the set's %llu spans",
-                (unsigned long long)in_traces[0], (unsigned long long)in_traces[1],
-                (unsigned long long)n);
-      in_traces[0] = in_traces[1] = 0;
-      local = ANOMOD_EINVAL;
-    }
-  }
+  // the spans that lie in traces (spans outside every trace are on no path:
+  // their cp_us and on_path read 0)
+  uint64_t in_traces[2];
+  local = trace_span_range(ctx, spans, in_traces);
+  if (local != ANOMOD_OK && local != ANOMOD_EINVAL) return local;
   const uint64_t n_in = in_traces[1] - in_traces[0];
 
-  // The call's workspace, freed when it returns (after the stream's work), as
-  // the self-time call's: a block of words (dynamic-tail counter, long-trace
+  // The call's workspace: a block of words (dynamic-tail counter, long-trace
   // counters, order-probe scratch) and a block of records | cp_us | on_path
   // (when asked for) | long-trace list | the listed spans' state (64 B per
   // span).  The long traces are counted first.
-  struct Workspace {
-    anomod_ctx* ctx;
-    void* words = nullptr;
-    void* block = nullptr;
-    ~Workspace() {
-      if (!words && !block) return;
-      (void)hipStreamSynchronize(ctx->stream);
-      if (words) (void)hipFree(words);
-      if (block) (void)hipFree(block);
-    }
-  } ws{ctx};
-  auto take = [&](void** p, size_t bytes) {
-    if (dev_malloc(ctx, p, bytes) == hipSuccess) return ANOMOD_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    set_error(ctx, "hipMalloc(%zu) for the critical-path workspace failed", bytes);
-    return ANOMOD_ENOMEM;
-  };
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  CallWorkspace ws{ctx};
+  const auto al = CallWorkspace::al;
   unsigned long long nlong[2] = {0ull, 0ull};
-  if (local == ANOMOD_OK && n_in) local = take(&ws.words, 256);
-  if (local == ANOMOD_OK && n_in && spans->max_trace_len > (uint64_t)kStage) {
-    auto* cnt = static_cast<unsigned long long*>(ws.words);
-    ANOMOD_HIP(ctx, hipMemsetAsync(cnt, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(cp_long_count_kernel,
-                       dim3((unsigned)std::min<uint64_t>((nt + 255) / 256, 4ull * ctx->num_cus)),
-                       dim3(256), 0, ctx->stream, spans->trace_ptr, nt, cnt);
-    ANOMOD_HIP(ctx, hipGetLastError());
-    ANOMOD_HIP(ctx, hipMemcpyAsync(nlong, cnt, 16, hipMemcpyDeviceToHost, ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if (local == ANOMOD_OK && n_in) local = ws.take(&ws.words, 256, "critical-path");
+  auto* words = static_cast<unsigned long long*>(ws.words);
+  if (local == ANOMOD_OK && n_in)
+    if (int rc = count_long_traces(ctx, spans, words, nlong)) return rc;
   const size_t nl = (size_t)nlong[1];
   const size_t b_rec = al(n * 8), b_cp = cp_us ? al(n * 4) : 0, b_on = on_path ? al(n) : 0;
   const size_t b_list = al(nlong[0] * 16), b_l8 = al(nl * 8), b_l4 = al(nl * 4);
   if (local == ANOMOD_OK && n_in)
-    local = take(&ws.block, b_rec + b_cp + b_on + b_list + 6 * b_l8 + 4 * b_l4);
+    local = ws.take(&ws.block, b_rec + b_cp + b_on + b_list + 6 * b_l8 + 4 * b_l4,
+                    "critical-path");
   if (int rc = comm_agree(ctx, local)) return rc;
 
   CpArgs a{};
   if (n_in) {
-    auto* words = static_cast<unsigned long long*>(ws.words);
-    char* w = static_cast<char*>(ws.block);
-    auto carve = [&](size_t bytes) {
-      char* p = w;
-      w += bytes;
-      return p;
-    };
-    a.rec = reinterpret_cast<unsigned long long*>(carve(b_rec));
-    a.cp_us = cp_us ? reinterpret_cast<uint32_t*>(carve(b_cp)) : nullptr;
-    a.on_path = on_path ? reinterpret_cast<uint8_t*>(carve(b_on)) : nullptr;
-    a.big_list = reinterpret_cast<unsigned long long*>(carve(b_list));
-    a.l_a = reinterpret_cast<unsigned long long*>(carve(b_l8));
-    a.l_b = reinterpret_cast<unsigned long long*>(carve(b_l8));
-    a.l_best = reinterpret_cast<unsigned long long*>(carve(b_l8));
-    a.l_cur = reinterpret_cast<unsigned long long*>(carve(b_l8));
-    a.l_j[0] = reinterpret_cast<unsigned long long*>(carve(b_l8));
-    a.l_j[1] = reinterpret_cast<unsigned long long*>(carve(b_l8));
-    a.l_ppos = reinterpret_cast<uint32_t*>(carve(b_l4));
-    a.l_bpos = reinterpret_cast<uint32_t*>(carve(b_l4));
-    a.l_sum = reinterpret_cast<uint32_t*>(carve(b_l4));
-    a.l_st = reinterpret_cast<uint32_t*>(carve(b_l4));
+    a.rec = ws.carve<unsigned long long>(b_rec);
+    a.cp_us = cp_us ? ws.carve<uint32_t>(b_cp) : nullptr;
+    a.on_path = on_path ? ws.carve<uint8_t>(b_on) : nullptr;
+    a.big_list = ws.carve<unsigned long long>(b_list);
+    a.l_a = ws.carve<unsigned long long>(b_l8);
+    a.l_b = ws.carve<unsigned long long>(b_l8);
+    a.l_best = ws.carve<unsigned long long>(b_l8);
+    a.l_cur = ws.carve<unsigned long long>(b_l8);
+    a.l_j[0] = ws.carve<unsigned long long>(b_l8);
+    a.l_j[1] = ws.carve<unsigned long long>(b_l8);
+    a.l_ppos = ws.carve<uint32_t>(b_l4);
+    a.l_bpos = ws.carve<uint32_t>(b_l4);
+    a.l_sum = ws.carve<uint32_t>(b_l4);
+    a.l_st = ws.carve<uint32_t>(b_l4);
     a.ctr = words;
     a.big = words + 1;
     a.big_cap = nlong[0];
     a.S = S;
-    // The scan the edge kernels would use for the set (its order hint is
-    // probed when unknown: the value the first aggregation would find).
-    bool uni = false;
-    if (int rc = span_scan_choice(ctx, spans, words + 4, &uni)) return rc;
-    const bool long_set = spans->max_trace_len != ~0ull && spans->max_trace_len > (uint64_t)kStage;
-    const int scan = !uni ? kScanFwd : (E > kNarrowRows || long_set) ? kScanSplit : kScanBidir;
+    int scan = kScanFwd;
+    if (int rc = pick_walk_scan(ctx, spans, S, words + 4, &scan)) return rc;
     const WalkFn fn = scan == kScanFwd     ? critical_path_kernel<kScanFwd>
                       : scan == kScanSplit ? critical_path_kernel<kScanSplit>
                                            : critical_path_kernel<kScanBidir>;
-    int per_cu = 0;
-    ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu, reinterpret_cast<const void*>(fn), kCpThreads, 0));
-    const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
-      fprintf(stderr, "anomod: critical-path kernel critical_path_kernel<%s>, %llu long traces\n",
-              scan == kScanFwd ? "forward" : scan == kScanSplit ? "split" : "bidir", nlong[0]);
+    uint64_t grid = 0;
+    if (int rc = walk_grid(ctx, fn, kCpThreads, &grid)) return rc;
+    log_walk_kernel("critical-path", "critical_path_kernel", scan, nlong[0]);
     ANOMOD_HIP(ctx, hipMemsetAsync(words, 0, 32, ctx->stream));  // ctr + big counters
     if (a.cp_us && n_in < n) ANOMOD_HIP(ctx, hipMemsetAsync(a.cp_us, 0, n * 4, ctx->stream));
     if (a.on_path && n_in < n) ANOMOD_HIP(ctx, hipMemsetAsync(a.on_path, 0, n, ctx->stream));

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "radix.h"
+#include "walk.h"
 
 namespace anomod {
 namespace {
@@ -237,20 +238,11 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   }
   ANOMOD_REQUIRE(ctx, spans->n_spans == 0 || spans->max_svc < S,
                  "span service index %u >= n_services %u", spans->max_svc, S);
-  // the spans that lie in traces: [trace_ptr[0], trace_ptr[n_traces])
-  uint64_t in_traces[2] = {0, 0};
-  if (spans->n_traces && spans->n_spans) {
+  // the spans that lie in traces
+  uint64_t in_traces[2];
+  if (spans->n_traces && spans->n_spans)
     if (int rc = bind(ctx)) return rc;
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces + 1, spans->trace_ptr + spans->n_traces, 8,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ANOMOD_REQUIRE(ctx, in_traces[0] <= in_traces[1] && in_traces[1] <= spans->n_spans,
-                   "trace_ptr range [%llu, %llu) outside the set's %llu spans",
-                   (unsigned long long)in_traces[0], (unsigned long long)in_traces[1],
-                   (unsigned long long)spans->n_spans);
-  }
+  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
   const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
   const uint64_t m = n ? n - in_traces[0] : 0;  // the spans that are sorted
   // one radix sort over the in-trace spans' keys (u32 tile offsets inside)
@@ -266,47 +258,27 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   }
   int cbits = 1;  // the sentinel cell T * E is a key too
   while ((uint64_t)TE >> cbits) ++cbits;
-  // The call's workspace, freed when it returns (after the stream's work), as
-  // the self-time call's: keys (widened in place) | sorted keys | sort temp |
-  // the key walk's words | misc + cell begins + cell ends (zeroed together) |
-  // count | q_us.
-  struct Workspace {
-    anomod_ctx* ctx;
-    void* block = nullptr;
-    ~Workspace() {
-      if (!block) return;
-      (void)hipStreamSynchronize(ctx->stream);
-      (void)hipFree(block);
-    }
-  } wsp{ctx};
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  // The call's workspace (freed when the call returns, after the stream's
+  // work): keys (widened in place) | sorted keys | sort temp | the key walk's
+  // words | misc + cell begins + cell ends (zeroed together) | count | q_us.
+  CallWorkspace wsp{ctx};
+  const auto al = CallWorkspace::al;
   const size_t sort_tmp = radix_temp_bytes(m);
   const size_t b_keys = al(n * 8), b_sorted = al(m * 8), b_tmp = al(sort_tmp),
                b_ws = al(span_edge_keys_ws_bytes(spans)), b_u32 = al((size_t)TE * 4),
                b_cnt = out->count ? al((size_t)TE * 8) : 0, b_q = al((size_t)TE * nq * 4);
   const size_t b_zero = 256 + 2 * b_u32;
   const size_t total = b_keys + b_sorted + b_tmp + b_ws + b_zero + b_cnt + b_q;
-  if (dev_malloc(ctx, &wsp.block, total) != hipSuccess) {
-    (void)hipGetLastError();
-    wsp.block = nullptr;
-    set_error(ctx, "hipMalloc(%zu) for the edge-window-quantile workspace failed", total);
-    return ANOMOD_ENOMEM;
-  }
-  char* w = static_cast<char*>(wsp.block);
-  auto carve = [&](size_t bytes) {
-    char* p = w;
-    w += bytes;
-    return p;
-  };
-  auto* keys = reinterpret_cast<unsigned long long*>(carve(b_keys));
-  auto* sorted = reinterpret_cast<unsigned long long*>(carve(b_sorted));
-  void* tmp = carve(b_tmp);
-  auto* walk = reinterpret_cast<unsigned long long*>(carve(b_ws));
-  auto* misc_d = reinterpret_cast<unsigned long long*>(carve(256));
-  auto* cbegin = reinterpret_cast<uint32_t*>(carve(b_u32));
-  auto* cend = reinterpret_cast<uint32_t*>(carve(b_u32));
-  auto* d_cnt = out->count ? reinterpret_cast<unsigned long long*>(carve(b_cnt)) : nullptr;
-  auto* d_q = reinterpret_cast<uint32_t*>(carve(b_q));
+  if (int rc = wsp.take(&wsp.block, total, "edge-window-quantile")) return rc;
+  auto* keys = wsp.carve<unsigned long long>(b_keys);
+  auto* sorted = wsp.carve<unsigned long long>(b_sorted);
+  void* tmp = wsp.carve(b_tmp);
+  auto* walk = wsp.carve<unsigned long long>(b_ws);
+  auto* misc_d = wsp.carve<unsigned long long>(256);
+  auto* cbegin = wsp.carve<uint32_t>(b_u32);
+  auto* cend = wsp.carve<uint32_t>(b_u32);
+  auto* d_cnt = out->count ? wsp.carve<unsigned long long>(b_cnt) : nullptr;
+  auto* d_q = wsp.carve<uint32_t>(b_q);
 
   ANOMOD_HIP(ctx, hipMemsetAsync(misc_d, 0, b_zero, ctx->stream));
   if (int rc = span_edge_keys(ctx, spans, S, keys, walk)) return rc;

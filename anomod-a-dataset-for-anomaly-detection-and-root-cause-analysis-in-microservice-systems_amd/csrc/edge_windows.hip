@@ -27,6 +27,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "walk.h"
 
 namespace anomod {
 namespace {
@@ -349,21 +350,12 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
   }
   ANOMOD_REQUIRE(ctx, spans->n_spans == 0 || spans->max_svc < S,
                  "span service index %u >= n_services %u", spans->max_svc, S);
-  // the spans that lie in traces: [trace_ptr[0], trace_ptr[n_traces]) (an upload may
-  // leave spans outside every trace: the aggregation counts none of them)
-  uint64_t in_traces[2] = {0, 0};
-  if (spans->n_traces && spans->n_spans) {
+  // the spans that lie in traces (an upload may leave spans outside every
+  // trace: the aggregation counts none of them)
+  uint64_t in_traces[2];
+  if (spans->n_traces && spans->n_spans)
     if (int rc = bind(ctx)) return rc;
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces + 1, spans->trace_ptr + spans->n_traces, 8,
-                                   hipMemcpyDeviceToHost, ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ANOMOD_REQUIRE(ctx, in_traces[0] <= in_traces[1] && in_traces[1] <= spans->n_spans,
-                   "trace_ptr range [%llu, %llu) outside the set's %llu spans",
-                   (unsigned long long)in_traces[0], (unsigned long long)in_traces[1],
-                   (unsigned long long)spans->n_spans);
-  }
+  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
   const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
   const uint64_t TE = (uint64_t)T * E;
   out->outside = 0;

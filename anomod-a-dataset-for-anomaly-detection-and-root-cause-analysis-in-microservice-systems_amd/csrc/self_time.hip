@@ -9,7 +9,7 @@
 //
 // Children overlapping in time are summed, not merged.
 //
-// One chunk walk (chunk.h: persistent waves, <= 256 spans / <= 64 whole
+// One chunk walk (walk.h: persistent waves, <= 256 spans / <= 64 whole
 // traces per chunk, buffer loads, the columns of chunk c+1 in flight while
 // chunk c is resolved) stages ids and services in the wave's LDS, finds every
 // span's parent *position*, adds the span's duration to the parent's u64
@@ -24,8 +24,8 @@
 #include <algorithm>
 #include <cstring>
 
-#include "chunk.h"
 #include "common.h"
+#include "walk.h"
 
 namespace anomod {
 namespace {
@@ -33,11 +33,6 @@ namespace {
 using namespace chunk;
 constexpr int kSelfWaves = 8;
 constexpr int kSelfThreads = kSelfWaves * kWave;
-// Tables wider than this many rows (TrainTicket: 48 * 46) and sets holding
-// long traces take the split-word scan, as the edge kernels do.
-constexpr uint32_t kNarrowRows = 512;
-enum Scan { kScanFwd = 0, kScanBidir = 1, kScanSplit = 2 };
-constexpr uint32_t kSplitFwd = 12, kSplitBwd = 4;  // edge_agg.hip kWFwd / kWBwd
 
 // Per-wave LDS (every offset a multiple of 16).
 constexpr int kSSid = 0;  // u64 span ids [kStage + kScanSlack], or two u32 planes of that length
@@ -83,32 +78,6 @@ __device__ __forceinline__ void load_regs(const uint64_t* __restrict__ span_id,
   }
 }
 
-// First span of [a, b) whose id equals pid (-1: none): the forward scan of
-// sets not declared unique, kFwdScan ids per step.
-constexpr uint32_t kFwdScan = 10;
-static_assert(kFwdScan % 2 == 0 && kFwdScan <= kScanSlack, "scan step");
-__device__ __forceinline__ int find_first(const uint64_t* lsid, uint32_t a, uint32_t b,
-                                          uint64_t pid) {
-  for (uint32_t q0 = a; q0 < b; q0 += kFwdScan) {
-    uint64_t v[kFwdScan];
-#pragma unroll
-    for (uint32_t j = 0; j < kFwdScan; ++j) v[j] = lsid[q0 + j];
-    uint32_t m = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kFwdScan; ++j) m |= (v[j] == pid ? 1u : 0u) << j;
-    const uint32_t hi = (b - q0) < kFwdScan ? (b - q0) : kFwdScan;  // >= 1
-    m &= (1u << hi) - 1u;
-    if (m) return (int)(q0 + __ffs(m) - 1u);
-  }
-  return -1;
-}
-
-__device__ __forceinline__ unsigned long long make_rec(uint32_t row, uint32_t S, uint32_t sf,
-                                                       uint32_t self) {
-  return ((unsigned long long)(row * S + (sf & 0xFFFFu)) << 33) |
-         ((unsigned long long)((sf >> 16) & ANOMOD_FLAG_ERROR ? 1u : 0u) << 32) | self;
-}
-
 template <int SCAN>
 __device__ __forceinline__ void self_chunk(unsigned char* wsm, int lane, const Chunk& c,
                                            const Regs& R, const SelfArgs& a) {
@@ -144,13 +113,7 @@ __device__ __forceinline__ void self_chunk(unsigned char* wsm, int lane, const C
       p = a.S + 1u;  // ORPHAN unless found in the trace
       uint32_t ta, tb;
       trace_bounds(Sm, r, lane, c.n, ta, tb);
-      int q;
-      if constexpr (SCAN == kScanSplit)
-        q = find_parent_split<kSplitFwd, kSplitBwd>(llo, lhi, ta, tb, i, R.pid[r]);
-      else if constexpr (SCAN == kScanBidir)
-        q = find_parent_bidir<kFwd, kBwd>(lsid, ta, tb, i, R.pid[r]);
-      else
-        q = find_first(lsid, ta, tb, R.pid[r]);
+      const int q = find_parent<SCAN>(lsid, llo, lhi, ta, tb, i, R.pid[r]);
       if (q >= 0) {
         p = lsvc[q];
         // a span is not its own child; its row keeps its own service as parent
@@ -167,7 +130,7 @@ __device__ __forceinline__ void self_chunk(unsigned char* wsm, int lane, const C
     const unsigned long long cs = lsum[i];
     const uint32_t d = R.dur[r];
     const uint32_t self = d - (cs < (unsigned long long)d ? (uint32_t)cs : d);
-    a.rec[c.base + i] = make_rec(row[r], a.S, R.sf[r], self);
+    a.rec[c.base + i] = edge_rec(row[r], a.S, R.sf[r], self);
     if (a.self_us) a.self_us[c.base + i] = self;
   }
   wave_sync();  // the staging area is free for the next chunk
@@ -180,126 +143,37 @@ __global__ __launch_bounds__(kSelfThreads) void self_time_kernel(
     const uint64_t* __restrict__ trace_ptr, uint64_t n_traces, SelfArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kSBytes * kSelfWaves];
   const int lane = threadIdx.x & (kWave - 1);
-  const int wid = threadIdx.x / kWave;
-  unsigned char* wsm = smem + wid * kSBytes;
-  const uint64_t gw = (uint64_t)blockIdx.x * kSelfWaves + wid;
-  const uint64_t nw = (uint64_t)gridDim.x * kSelfWaves;
-  auto run = [&](const uint64_t t_begin, const uint64_t t_end) __attribute__((always_inline)) {
-    // Software pipeline (as the edge kernel): the bounds of chunk c+2 and the
-    // span columns of chunk c+1 are in flight while chunk c is resolved.
-    uint64_t lo, hi;
-    load_bounds(trace_ptr, t_begin, t_end, lane, lo, hi);
-    Chunk cur = make_chunk(t_begin, t_end, lane, lo, hi);
-    uint64_t t_cur = t_begin;
-    Regs R;
-    load_regs(span_id, parent, svcfl, dur, cur, lane, R);
-    uint64_t t_next = t_begin + (cur.k ? cur.k : 1u);
-    load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-    while (true) {
-      const bool has_next = t_next < t_end;
-      const uint64_t t_nxt = t_next;
-      Chunk nxt{};
-      Regs Rn;
-      if (has_next) {
-        nxt = make_chunk(t_next, t_end, lane, lo, hi);
-        load_regs(span_id, parent, svcfl, dur, nxt, lane, Rn);
-        t_next += nxt.k ? nxt.k : 1u;
-        load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-      }
-      if (cur.k == 0) {  // longer than kStage: listed for self_big_kernel
-        if (lane == 0) {
-          const unsigned long long j = atomicAdd(&a.big[0], 1ull);
-          if (j < a.big_cap) {  // (always: the list is sized to the counted long traces)
-            a.big_list[2 * j] = t_cur;
-            a.big_list[2 * j + 1] = atomicAdd(&a.big[1], (unsigned long long)cur.n);
-          }
-        }
-      } else {
-        self_chunk<SCAN>(wsm, lane, cur, R, a);
-      }
-      if (!has_next) break;
-      cur = nxt;
-      t_cur = t_nxt;
-      R = Rn;
-    }
-  };
-  // As the edge kernel: a static share per wave, then the last 1 / kDyn of
-  // the traces in segments of kDynSeg from a global counter.
-  constexpr uint64_t kDyn = 4, kDynSeg = 512;
-  const uint64_t n_static = n_traces - n_traces / kDyn;
-  uint64_t t_begin = uniform64(n_static * gw / nw);
-  uint64_t t_end = uniform64(n_static * (gw + 1) / nw);
-  while (true) {
-    if (t_begin < t_end) run(t_begin, t_end);
-    if (n_static == n_traces) break;
-    unsigned long long g = 0;
-    if (lane == 0) g = atomicAdd(a.ctr, (unsigned long long)kDynSeg);
-    g = __shfl(g, 0);
-    t_begin = uniform64(n_static + g);
-    if (t_begin >= n_traces) break;
-    t_end = uniform64(t_begin + kDynSeg < n_traces ? t_begin + kDynSeg : n_traces);
-  }
+  unsigned char* wsm = smem + (threadIdx.x / kWave) * kSBytes;
+  walk_traces<kSelfWaves, 4, Regs>(
+      trace_ptr, n_traces, a.ctr,
+      [&](const Chunk& c, Regs& R) __attribute__((always_inline)) {
+        load_regs(span_id, parent, svcfl, dur, c, lane, R);
+      },
+      [&](const Chunk& c, uint32_t, uint64_t, const Regs& R) __attribute__((always_inline)) {
+        self_chunk<SCAN>(wsm, lane, c, R, a);
+      },
+      // longer than kStage: listed for self_big_kernel
+      [&](uint64_t t, uint32_t n) __attribute__((always_inline)) {
+        list_long(a.big, a.big_list, a.big_cap, lane, t, n);
+      });
 }
 
 // ---- long traces ----------------------------------------------------------
-// Traces and spans of the set that outgrow a chunk: cnt[0] traces, cnt[1]
-// spans (sizes the list and the child-sum scratch before the walk).
-__global__ __launch_bounds__(256) void self_long_count_kernel(const uint64_t* __restrict__ trace_ptr,
-                                                              uint64_t n_traces,
-                                                              unsigned long long* __restrict__ cnt) {
-  unsigned long long nt = 0, ns = 0;
-  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n_traces;
-       t += (uint64_t)gridDim.x * 256) {
-    const uint64_t L = trace_ptr[t + 1] - trace_ptr[t];
-    if (L > (uint64_t)kStage) {
-      nt += 1;
-      ns += L;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    nt += __shfl_xor(nt, o);
-    ns += __shfl_xor(ns, o);
-  }
-  if ((threadIdx.x & 63) == 0 && nt) {
-    atomicAdd(&cnt[0], nt);
-    atomicAdd(&cnt[1], ns);
-  }
-}
-
-// One workgroup per listed trace.  Parent positions come from an LDS hash
-// table over a window of kBigWin ids (id -> first position in the window):
-// a block of kBigThreads * kBigPer spans probes the trace's windows in trace
-// order, so the first window holding an id gives its first occurrence —
-// ceil(L / block) * ceil(L / kBigWin) window builds of kBigWin inserts each,
-// O(L^2 / block) LDS inserts for a trace of L spans.  Child sums go to the
-// u64 scratch by global atomics, the spans' records hold (row, error,
-// dur_us) meanwhile, and a final sweep by the same threads turns dur_us into
-// self_us.
-constexpr int kBigThreads = 512;
-constexpr int kBigPer = 8;
-constexpr uint32_t kBigWin = 2048;
-constexpr uint32_t kBigSlots = 2 * kBigWin;  // load <= 1/2
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-static_assert((kBigSlots & (kBigSlots - 1)) == 0, "power-of-two table");
-
-__device__ __forceinline__ uint32_t big_slot(uint64_t id) {
-  return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32) & (kBigSlots - 1u);
-}
-
+// One workgroup per listed trace.  Parent positions come from walk.h's
+// windowed LDS id table (big_parents).  Child sums go to the u64 scratch by
+// global atomics, the spans' records hold (row, error, dur_us) meanwhile, and
+// a final sweep by the same threads turns dur_us into self_us.
 __global__ __launch_bounds__(kBigThreads) void self_big_kernel(
     const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
     const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
     const uint64_t* __restrict__ trace_ptr, SelfArgs a) {
-  __shared__ unsigned long long bkey[kBigSlots];  // 0 = empty (id 0 is never a parent reference)
-  __shared__ uint32_t bpos[kBigSlots];            // first position in the window
+  __shared__ unsigned long long bkey[kBigSlots];
+  __shared__ uint32_t bpos[kBigSlots];
   __shared__ unsigned long long s_j;
   const int tid = threadIdx.x;
   const uint64_t nbig = a.big[0] < a.big_cap ? a.big[0] : a.big_cap;
   const uint32_t S = a.S;
-  for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-    bkey[k] = 0ull;
-    bpos[k] = kNone;
-  }
+  big_clear(bkey, bpos, tid);
   while (true) {
     __syncthreads();
     if (tid == 0) s_j = atomicAdd(&a.big[2], 1ull);
@@ -310,54 +184,13 @@ __global__ __launch_bounds__(kBigThreads) void self_big_kernel(
     unsigned long long* csum = a.csum + a.big_list[2 * j + 1];
     const uint64_t lo = trace_ptr[t];
     const uint32_t L = (uint32_t)(trace_ptr[t + 1] - lo);  // the call takes < 2^32 spans
-    for (uint32_t b0 = 0; b0 < L; b0 += kBigThreads * kBigPer) {
+    for (uint64_t b0 = 0; b0 < L; b0 += kBigThreads * kBigPer) {
       uint64_t pid[kBigPer];
-      uint32_t pp[kBigPer];  // parent position in the trace (kNone: not found yet)
-      bool need = false;
+      uint32_t pp[kBigPer];  // parent position in the trace (kNone: none)
+      big_parents(span_id, parent, lo, L, b0, tid, bkey, bpos, pid, pp);
 #pragma unroll
       for (int r = 0; r < kBigPer; ++r) {
-        const uint32_t i = b0 + (uint32_t)r * kBigThreads + tid;
-        pid[r] = i < L ? parent[lo + i] : 0ull;
-        pp[r] = kNone;
-        need |= pid[r] != 0ull;
-      }
-      for (uint32_t w0 = 0; w0 < L; w0 += kBigWin) {
-        if (!__syncthreads_or(need)) break;  // also orders the previous clear
-        for (uint32_t k = tid; k < kBigWin && w0 + k < L; k += kBigThreads) {
-          const uint64_t id = span_id[lo + w0 + k];
-          if (id == 0ull) continue;
-          for (uint32_t sl = big_slot(id);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-            const unsigned long long prev = atomicCAS(&bkey[sl], 0ull, (unsigned long long)id);
-            if (prev == 0ull || prev == id) {
-              atomicMin(&bpos[sl], k);  // the first position wins
-              break;
-            }
-          }
-        }
-        __syncthreads();
-        need = false;
-#pragma unroll
-        for (int r = 0; r < kBigPer; ++r) {
-          if (pid[r] == 0ull || pp[r] != kNone) continue;
-          for (uint32_t sl = big_slot(pid[r]);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-            const unsigned long long key = bkey[sl];
-            if (key == pid[r]) {
-              pp[r] = w0 + bpos[sl];
-              break;
-            }
-            if (key == 0ull) break;
-          }
-          need |= pp[r] == kNone;
-        }
-        __syncthreads();
-        for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-          bkey[k] = 0ull;
-          bpos[k] = kNone;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < kBigPer; ++r) {
-        const uint32_t i = b0 + (uint32_t)r * kBigThreads + tid;
+        const uint64_t i = b0 + (uint64_t)r * kBigThreads + tid;
         if (i >= L) continue;
         const uint32_t sf = svcfl[lo + i], d = dur[lo + i];
         uint32_t p = S;
@@ -368,16 +201,16 @@ __global__ __launch_bounds__(kBigThreads) void self_big_kernel(
             if (pp[r] != i) atomicAdd(&csum[pp[r]], (unsigned long long)d);
           }
         }
-        a.rec[lo + i] = make_rec(p, S, sf, d);
+        a.rec[lo + i] = edge_rec(p, S, sf, d);
       }
     }
     // every child sum of the trace landed (this workgroup made all of them)
     __threadfence();
     __syncthreads();
-    for (uint32_t b0 = 0; b0 < L; b0 += kBigThreads * kBigPer) {
+    for (uint64_t b0 = 0; b0 < L; b0 += kBigThreads * kBigPer) {
 #pragma unroll
       for (int r = 0; r < kBigPer; ++r) {
-        const uint32_t i = b0 + (uint32_t)r * kBigThreads + tid;
+        const uint64_t i = b0 + (uint64_t)r * kBigThreads + tid;
         if (i >= L) continue;
         const unsigned long long x = a.rec[lo + i];  // this thread's own store
         const unsigned long long cs =
@@ -426,98 +259,49 @@ int anomod_edge_self_time_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   if (int rc = comm_agree(ctx, local)) return rc;
 
   const uint64_t n = spans->n_spans, nt = spans->n_traces;
-  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
-  // the spans that lie in traces: [trace_ptr[0], trace_ptr[n_traces]) (an
-  // upload may leave spans outside every trace: they are on no edge and their
-  // self_us reads 0)
-  uint64_t in_traces[2] = {0, 0};
-  if (nt && n) {
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces + 1, spans->trace_ptr + nt, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (!(in_traces[0] <= in_traces[1] && in_traces[1] <= n)) {
-      set_error(ctx, "trace_ptr range [%llu, %llu) outside the set's %llu spans",
-                (unsigned long long)in_traces[0], (unsigned long long)in_traces[1],
-                (unsigned long long)n);
-      in_traces[0] = in_traces[1] = 0;
-      local = ANOMOD_EINVAL;
-    }
-  }
+  // the spans that lie in traces (an upload may leave spans outside every
+  // trace: they are on no edge and their self_us reads 0)
+  uint64_t in_traces[2];
+  local = trace_span_range(ctx, spans, in_traces);
+  if (local != ANOMOD_OK && local != ANOMOD_EINVAL) return local;
   const uint64_t n_rec = in_traces[1] - in_traces[0];
 
-  // The call's workspace, freed when it returns (after the stream's work):
-  // a block of words (dynamic-tail counter, long-trace counters, order-probe
-  // scratch, long-trace count) and a block of records | self_us (when asked
-  // for) | long-trace list | child sums of the listed spans.  The long traces
-  // are counted first (one small kernel and a host wait, skipped when the
-  // set's longest trace is known to fit a chunk), so the list and the child
-  // sums are sized to them.
-  struct Workspace {
-    anomod_ctx* ctx;
-    void* words = nullptr;
-    void* block = nullptr;
-    ~Workspace() {
-      if (!words && !block) return;
-      (void)hipStreamSynchronize(ctx->stream);
-      if (words) (void)hipFree(words);
-      if (block) (void)hipFree(block);
-    }
-  } ws{ctx};
-  auto take = [&](void** p, size_t bytes) {
-    if (dev_malloc(ctx, p, bytes) == hipSuccess) return ANOMOD_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    set_error(ctx, "hipMalloc(%zu) for the self-time workspace failed", bytes);
-    return ANOMOD_ENOMEM;
-  };
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  // The call's workspace: a block of words (dynamic-tail counter, long-trace
+  // counters, order-probe scratch, long-trace count) and a block of records |
+  // self_us (when asked for) | long-trace list | child sums of the listed
+  // spans.  The long traces are counted first, so the list and the child sums
+  // are sized to them.
+  CallWorkspace ws{ctx};
+  const auto al = CallWorkspace::al;
   unsigned long long nlong[2] = {0ull, 0ull};
-  if (local == ANOMOD_OK && n_rec) local = take(&ws.words, 256);
-  if (local == ANOMOD_OK && n_rec && spans->max_trace_len > (uint64_t)kStage) {
-    auto* cnt = static_cast<unsigned long long*>(ws.words);
-    ANOMOD_HIP(ctx, hipMemsetAsync(cnt, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(self_long_count_kernel,
-                       dim3((unsigned)std::min<uint64_t>((nt + 255) / 256, 4ull * ctx->num_cus)),
-                       dim3(256), 0, ctx->stream, spans->trace_ptr, nt, cnt);
-    ANOMOD_HIP(ctx, hipGetLastError());
-    ANOMOD_HIP(ctx, hipMemcpyAsync(nlong, cnt, 16, hipMemcpyDeviceToHost, ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if (local == ANOMOD_OK && n_rec) local = ws.take(&ws.words, 256, "self-time");
+  auto* words = static_cast<unsigned long long*>(ws.words);
+  if (local == ANOMOD_OK && n_rec)
+    if (int rc = count_long_traces(ctx, spans, words, nlong)) return rc;
   const size_t b_rec = al(n * 8), b_self = self_us ? al(n * 4) : 0;
   const size_t b_list = al(nlong[0] * 16), b_csum = al(nlong[1] * 8);
-  if (local == ANOMOD_OK && n_rec) local = take(&ws.block, b_rec + b_self + b_list + b_csum);
+  if (local == ANOMOD_OK && n_rec)
+    local = ws.take(&ws.block, b_rec + b_self + b_list + b_csum, "self-time");
   if (int rc = comm_agree(ctx, local)) return rc;
 
   SelfArgs a{};
   if (n_rec) {
-    auto* words = static_cast<unsigned long long*>(ws.words);
-    char* w = static_cast<char*>(ws.block);
-    a.rec = reinterpret_cast<unsigned long long*>(w);
-    a.self_us = self_us ? reinterpret_cast<uint32_t*>(w + b_rec) : nullptr;
+    a.rec = ws.carve<unsigned long long>(b_rec);
+    a.self_us = self_us ? ws.carve<uint32_t>(b_self) : nullptr;
+    a.big_list = ws.carve<unsigned long long>(b_list);
+    a.csum = ws.carve<unsigned long long>(b_csum);
     a.ctr = words;
     a.big = words + 1;
-    a.big_list = reinterpret_cast<unsigned long long*>(w + b_rec + b_self);
     a.big_cap = nlong[0];
-    a.csum = reinterpret_cast<unsigned long long*>(w + b_rec + b_self + b_list);
     a.S = S;
-    // The scan the edge kernels would use for the set (its order hint is
-    // probed when unknown: the value the first aggregation would find).
-    bool uni = false;
-    if (int rc = span_scan_choice(ctx, spans, words + 4, &uni)) return rc;
-    const bool long_set = spans->max_trace_len != ~0ull && spans->max_trace_len > (uint64_t)kStage;
-    const int scan = !uni ? kScanFwd : (E > kNarrowRows || long_set) ? kScanSplit : kScanBidir;
+    int scan = kScanFwd;
+    if (int rc = pick_walk_scan(ctx, spans, S, words + 4, &scan)) return rc;
     const WalkFn fn = scan == kScanFwd     ? self_time_kernel<kScanFwd>
                       : scan == kScanSplit ? self_time_kernel<kScanSplit>
                                            : self_time_kernel<kScanBidir>;
-    int per_cu = 0;
-    ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu, reinterpret_cast<const void*>(fn), kSelfThreads, 0));
-    const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
-      fprintf(stderr, "anomod: self-time kernel self_time_kernel<%s>, %llu long traces\n",
-              scan == kScanFwd ? "forward" : scan == kScanSplit ? "split" : "bidir", nlong[0]);
+    uint64_t grid = 0;
+    if (int rc = walk_grid(ctx, fn, kSelfThreads, &grid)) return rc;
+    log_walk_kernel("self-time", "self_time_kernel", scan, nlong[0]);
     ANOMOD_HIP(ctx, hipMemsetAsync(words, 0, 32, ctx->stream));  // ctr + big counters
     if (nlong[1]) ANOMOD_HIP(ctx, hipMemsetAsync(a.csum, 0, nlong[1] * 8, ctx->stream));
     if (a.self_us && n_rec < n) ANOMOD_HIP(ctx, hipMemsetAsync(a.self_us, 0, n * 4, ctx->stream));

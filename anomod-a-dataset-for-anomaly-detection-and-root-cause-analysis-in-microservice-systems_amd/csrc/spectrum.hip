@@ -9,7 +9,7 @@
 //
 // Two passes.  Pass 1 is the aggregation kernels' own walk in its key form
 // (span_edge_keys, edge_agg.hip): keys[i] = row << 32 | dur_us by span
-// position.  Pass 2 (spectrum_kernel) is a chunk walk (chunk.h: persistent
+// position.  Pass 2 (spectrum_kernel) is a chunk walk (walk.h: persistent
 // waves, <= 256 spans / <= 64 whole traces per chunk, the columns of chunk
 // c+1 in flight while chunk c is resolved) that reads 12 B per span (key 8,
 // svc|flags 4) and 8 B per trace, and writes 1 B per trace:
@@ -39,8 +39,8 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "chunk.h"
 #include "common.h"
+#include "walk.h"
 
 namespace anomod {
 namespace {
@@ -85,21 +85,6 @@ extern __shared__ __align__(16) unsigned char spec_lds[];
 __device__ __forceinline__ bool span_bad(const SpecArgs& a, uint32_t row, uint32_t dur, uint32_t sf) {
   const uint32_t thr = a.thr ? a.thr[row] : kU32Max;
   return dur > thr || (a.use_errors && ((sf >> 16) & ANOMOD_FLAG_ERROR));
-}
-
-// Index, among the chunk's trace-start flags, of the last flag at or before
-// position s (< kStage): trace_in_chunk for a position that is not the lane's.
-__device__ __forceinline__ uint32_t rank_at(const uint64_t (&Sm)[kPer], uint32_t s) {
-  const uint32_t q = s >> 6, b = s & 63u;
-  uint32_t before = 0;
-  uint64_t m = Sm[0];
-#pragma unroll
-  for (int j = 1; j < kPer; ++j) {
-    before += q >= (uint32_t)j ? (uint32_t)__popcll(Sm[j - 1]) : 0u;
-    m = q >= (uint32_t)j ? Sm[j] : m;
-  }
-  const uint64_t le = b == 63u ? ~0ull : ((2ull << b) - 1ull);
-  return before + (uint32_t)__popcll(m & le) - 1u;
 }
 
 struct Regs {
@@ -220,60 +205,17 @@ __global__ __launch_bounds__(kSpThreads) void spectrum_kernel(
       lctr[n_ctr + k] = a.thr ? a.thr[k] : kU32Max;
   }
   __syncthreads();
-  const uint64_t gw = (uint64_t)blockIdx.x * kSpWaves + wid;
-  const uint64_t nw = (uint64_t)gridDim.x * kSpWaves;
   unsigned long long nT[2] = {0ull, 0ull};
   uint32_t invalid = 0;
-  auto run = [&](const uint64_t t_begin, const uint64_t t_end) __attribute__((always_inline)) {
-    // Software pipeline (as the edge kernel): the bounds of chunk c+2 and the
-    // span columns of chunk c+1 are in flight while chunk c is resolved.
-    uint64_t lo, hi;
-    load_bounds(trace_ptr, t_begin, t_end, lane, lo, hi);
-    Chunk cur = make_chunk(t_begin, t_end, lane, lo, hi);
-    uint32_t end_cur = (uint32_t)(hi - cur.base);
-    uint64_t t_cur = t_begin;
-    Regs R;
-    load_regs(a, cur, lane, R);
-    uint64_t t_next = t_begin + (cur.k ? cur.k : 1u);
-    load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-    while (true) {
-      const bool has_next = t_next < t_end;
-      const uint64_t t_nxt = t_next;
-      Chunk nxt{};
-      uint32_t end_nxt = 0;
-      Regs Rn;
-      if (has_next) {
-        nxt = make_chunk(t_next, t_end, lane, lo, hi);
-        end_nxt = (uint32_t)(hi - nxt.base);
-        load_regs(a, nxt, lane, Rn);
-        t_next += nxt.k ? nxt.k : 1u;
-        load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-      }
-      // (k == 0: longer than kStage, spectrum_long_kernel's)
-      if (cur.k) spectrum_chunk(wsm, lsvc, lctr, lthr, lane, cur, end_cur, t_cur, R, a, nT, invalid);
-      if (!has_next) break;
-      cur = nxt;
-      end_cur = end_nxt;
-      t_cur = t_nxt;
-      R = Rn;
-    }
-  };
-  // As the edge kernel: a static share per wave, then the last 1 / kDyn of
-  // the traces in segments of kDynSeg from a global counter.
-  constexpr uint64_t kDyn = 4, kDynSeg = 512;
-  const uint64_t n_static = n_traces - n_traces / kDyn;
-  uint64_t t_begin = uniform64(n_static * gw / nw);
-  uint64_t t_end = uniform64(n_static * (gw + 1) / nw);
-  while (true) {
-    if (t_begin < t_end) run(t_begin, t_end);
-    if (n_static == n_traces) break;
-    unsigned long long g = 0;
-    if (lane == 0) g = atomicAdd(a.ctr, (unsigned long long)kDynSeg);
-    g = __shfl(g, 0);
-    t_begin = uniform64(n_static + g);
-    if (t_begin >= n_traces) break;
-    t_end = uniform64(t_begin + kDynSeg < n_traces ? t_begin + kDynSeg : n_traces);
-  }
+  walk_traces<kSpWaves, 4, Regs>(
+      trace_ptr, n_traces, a.ctr,
+      [&](const Chunk& c, Regs& R) __attribute__((always_inline)) { load_regs(a, c, lane, R); },
+      [&](const Chunk& c, uint32_t end, uint64_t t0, const Regs& R)
+          __attribute__((always_inline)) {
+            spectrum_chunk(wsm, lsvc, lctr, lthr, lane, c, end, t0, R, a, nT, invalid);
+          },
+      // longer than kStage: spectrum_long_kernel's
+      [](uint64_t, uint32_t) __attribute__((always_inline)) {});
   for (int o = 32; o > 0; o >>= 1) invalid += (uint32_t)__shfl_xor((int)invalid, o);
   if (lane == 0) {
     if (nT[0]) atomicAdd(a.misc, nT[0]);
@@ -390,20 +332,10 @@ int anomod_trace_spectrum_spans(anomod_ctx* ctx, const anomod_spans* spans,
                  (unsigned long long)spans->n_spans);
   if (int rc = bind(ctx)) return rc;
   const uint64_t nt = spans->n_traces;
-  // the spans that lie in traces: [trace_ptr[0], trace_ptr[n_traces]) (an upload may
-  // leave spans outside every trace: the aggregation counts none of them)
-  uint64_t in_traces[2] = {0, 0};
-  if (nt && spans->n_spans) {
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces + 1, spans->trace_ptr + nt, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ANOMOD_REQUIRE(ctx, in_traces[0] <= in_traces[1] && in_traces[1] <= spans->n_spans,
-                   "anomod_trace_spectrum_spans: trace_ptr range [%llu, %llu) outside the set's "
-                   "%llu spans", (unsigned long long)in_traces[0],
-                   (unsigned long long)in_traces[1], (unsigned long long)spans->n_spans);
-  }
+  // the spans that lie in traces (an upload may leave spans outside every
+  // trace: the aggregation counts none of them)
+  uint64_t in_traces[2];
+  if (int rc = trace_span_range(ctx, spans, in_traces, "anomod_trace_spectrum_spans: ")) return rc;
   const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
   const size_t n_tab = 3ull * E + 2ull * S;
   out->n_traces[0] = out->n_traces[1] = 0;
@@ -421,11 +353,12 @@ int anomod_trace_spectrum_spans(anomod_ctx* ctx, const anomod_spans* spans,
   // invalid keys) + the tables (zeroed together) | thresholds | class bytes.
   const char* lg = getenv("ANOMOD_LOG_KERNEL");  // (tests, timing)
   const bool log = lg && lg[0] == '1';
-  struct Workspace {
+  // (walk.h's CallWorkspace with the two times logged)
+  struct TimedBlock {
     anomod_ctx* ctx;
     bool log;
     void* block = nullptr;
-    ~Workspace() {
+    ~TimedBlock() {
       if (!block) return;
       (void)hipStreamSynchronize(ctx->stream);
       const double t0 = host_now_ms();
@@ -479,10 +412,8 @@ int anomod_trace_spectrum_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
     (void)hipGetLastError();
   }
-  int per_cu = 0;
-  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                      &per_cu, reinterpret_cast<const void*>(spectrum_kernel), kSpThreads, dyn));
-  const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
+  uint64_t grid = 0;
+  if (int rc = walk_grid(ctx, spectrum_kernel, kSpThreads, &grid, dyn)) return rc;
   // (unknown longest trace: the long pass looks for itself)
   const bool long_pass = spans->max_trace_len > (uint64_t)kStage;
   if (log)

@@ -23,9 +23,9 @@
 // round).  ceil(log2 L) rounds finish every on-tree span of a trace of L
 // spans; what is not done after them is off the tree.
 //
-// One chunk walk (chunk.h, as critical_path.hip: persistent waves, <= 256
-// spans / <= 64 whole traces per chunk, buffer loads, the columns of chunk c+1
-// in flight while chunk c is resolved) finds the parent positions in the
+// One chunk walk (walk.h: persistent waves, <= 256 spans / <= 64 whole traces
+// per chunk, buffer loads, the columns of chunk c+1 in flight while chunk c is
+// resolved) finds the parent positions in the
 // wave's LDS, runs at most 8 rounds there and adds every on-tree span's
 // mix64(P) to its trace's u64 LDS slot.  Traces longer than a chunk are listed
 // by the walk and resolved by trace_shapes_big_kernel, one workgroup per listed
@@ -38,10 +38,10 @@
 #include <cstring>
 #include <vector>
 
-#include "chunk.h"
 #include "common.h"
 #include "group.h"
 #include "radix.h"
+#include "walk.h"
 
 namespace anomod {
 namespace {
@@ -49,10 +49,6 @@ namespace {
 using namespace chunk;
 constexpr int kShWaves = 4;
 constexpr int kShThreads = kShWaves * kWave;
-// The scan dispatch of the edge kernels and of self_time.hip.
-constexpr uint32_t kNarrowRows = 512;
-enum Scan { kScanFwd = 0, kScanBidir = 1, kScanSplit = 2 };
-constexpr uint32_t kSplitFwd = 12, kSplitBwd = 4;
 
 constexpr uint64_t kB = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t kSeedRoot = 0x243F6A8885A308D3ull;
@@ -70,7 +66,6 @@ constexpr int kHFlag = kHSlot + kWave * 8;   // u8 trace-start flags [kStage]
 constexpr int kHBytes = kHFlag + kStage;
 static_assert(kHBytes % 16 == 0, "wave staging must stay 16-B aligned");
 
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 // chunk ancestor word: ancestor position, or kDone (P(i) = H)
 constexpr uint32_t kPosMask = 0xFFFFu, kDone = 1u << 17;
 // long-trace ancestor word: position in the trace, or kDoneBig
@@ -112,42 +107,6 @@ __device__ __forceinline__ void load_regs(const uint64_t* __restrict__ span_id,
     R.pid[r] = bload64(rpid, i * 8u);
     R.sf[r] = bload32(rsf, i * 4u);
   }
-}
-
-// First span of [a, b) whose id equals pid (-1: none): the forward scan of
-// sets not declared unique (self_time.hip find_first).
-constexpr uint32_t kFwdScan = 10;
-static_assert(kFwdScan % 2 == 0 && kFwdScan <= kScanSlack, "scan step");
-__device__ __forceinline__ int find_first(const uint64_t* lsid, uint32_t a, uint32_t b,
-                                          uint64_t pid) {
-  for (uint32_t q0 = a; q0 < b; q0 += kFwdScan) {
-    uint64_t v[kFwdScan];
-#pragma unroll
-    for (uint32_t j = 0; j < kFwdScan; ++j) v[j] = lsid[q0 + j];
-    uint32_t m = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kFwdScan; ++j) m |= (v[j] == pid ? 1u : 0u) << j;
-    const uint32_t hi = (b - q0) < kFwdScan ? (b - q0) : kFwdScan;  // >= 1
-    m &= (1u << hi) - 1u;
-    if (m) return (int)(q0 + __ffs(m) - 1u);
-  }
-  return -1;
-}
-
-// Index, among the chunk's trace-start flags, of the last flag at or before
-// position s (< kStage): trace_in_chunk for a position that is not the lane's
-// (spectrum.hip rank_at).
-__device__ __forceinline__ uint32_t rank_at(const uint64_t (&Sm)[kPer], uint32_t s) {
-  const uint32_t q = s >> 6, b = s & 63u;
-  uint32_t before = 0;
-  uint64_t m = Sm[0];
-#pragma unroll
-  for (int j = 1; j < kPer; ++j) {
-    before += q >= (uint32_t)j ? (uint32_t)__popcll(Sm[j - 1]) : 0u;
-    m = q >= (uint32_t)j ? Sm[j] : m;
-  }
-  const uint64_t le = b == 63u ? ~0ull : ((2ull << b) - 1ull);
-  return before + (uint32_t)__popcll(m & le) - 1u;
 }
 
 __device__ __forceinline__ uint64_t label_key(const ShArgs& a, uint32_t sf) {
@@ -198,12 +157,7 @@ __device__ __forceinline__ void shapes_chunk(unsigned char* wsm, int lane, const
       seed = kSeedOrphan;  // unless found in the trace
       uint32_t ta, tb;
       trace_bounds(Sm, r, lane, c.n, ta, tb);
-      if constexpr (SCAN == kScanSplit)
-        q = find_parent_split<kSplitFwd, kSplitBwd>(llo, lhi, ta, tb, i, R.pid[r]);
-      else if constexpr (SCAN == kScanBidir)
-        q = find_parent_bidir<kFwd, kBwd>(lsid, ta, tb, i, R.pid[r]);
-      else
-        q = find_first(lsid, ta, tb, R.pid[r]);
+      q = find_parent<SCAN>(lsid, llo, lhi, ta, tb, i, R.pid[r]);
       if ((uint32_t)q == i) seed = kSeedSelf;
     }
     const bool has = q >= 0 && (uint32_t)q != i;
@@ -282,148 +236,44 @@ __global__ __launch_bounds__(kShThreads, 3) void trace_shapes_kernel(
     ShArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[kHBytes * kShWaves];
   const int lane = threadIdx.x & (kWave - 1);
-  const int wid = threadIdx.x / kWave;
-  unsigned char* wsm = smem + wid * kHBytes;
-  const uint64_t gw = (uint64_t)blockIdx.x * kShWaves + wid;
-  const uint64_t nw = (uint64_t)gridDim.x * kShWaves;
+  unsigned char* wsm = smem + (threadIdx.x / kWave) * kHBytes;
   uint32_t off = 0;
-  auto run = [&](const uint64_t t_begin, const uint64_t t_end) __attribute__((always_inline)) {
-    // Software pipeline (as the edge kernel): the bounds of chunk c+2 and the
-    // span columns of chunk c+1 are in flight while chunk c is resolved.
-    uint64_t lo, hi;
-    load_bounds(trace_ptr, t_begin, t_end, lane, lo, hi);
-    Chunk cur = make_chunk(t_begin, t_end, lane, lo, hi);
-    uint32_t end_cur = (uint32_t)(hi - cur.base);
-    uint64_t t_cur = t_begin;
-    Regs R;
-    load_regs(span_id, parent, svcfl, cur, lane, R);
-    uint64_t t_next = t_begin + (cur.k ? cur.k : 1u);
-    load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-    while (true) {
-      const bool has_next = t_next < t_end;
-      const uint64_t t_nxt = t_next;
-      Chunk nxt{};
-      uint32_t end_nxt = 0;
-      Regs Rn;
-      if (has_next) {
-        nxt = make_chunk(t_next, t_end, lane, lo, hi);
-        end_nxt = (uint32_t)(hi - nxt.base);
-        load_regs(span_id, parent, svcfl, nxt, lane, Rn);
-        t_next += nxt.k ? nxt.k : 1u;
-        load_bounds(trace_ptr, t_next, t_end, lane, lo, hi);
-      }
-      if (cur.k == 0) {  // longer than kStage: listed for trace_shapes_big_kernel
-        if (lane == 0) {
-          const unsigned long long j = atomicAdd(&a.big[0], 1ull);
-          if (j < a.big_cap) {  // (always: the list is sized to the counted long traces)
-            a.big_list[2 * j] = t_cur;
-            a.big_list[2 * j + 1] = atomicAdd(&a.big[1], (unsigned long long)cur.n);
-          }
-        }
-      } else {
-        shapes_chunk<SCAN>(wsm, lane, cur, end_cur, t_cur, R, a, off);
-      }
-      if (!has_next) break;
-      cur = nxt;
-      end_cur = end_nxt;
-      t_cur = t_nxt;
-      R = Rn;
-    }
-  };
-  // As the edge kernel: a static share per wave, then the last 1 / kDyn of
-  // the traces in segments of kDynSeg from a global counter.
-  constexpr uint64_t kDyn = 4, kDynSeg = 512;
-  const uint64_t n_static = n_traces - n_traces / kDyn;
-  uint64_t t_begin = uniform64(n_static * gw / nw);
-  uint64_t t_end = uniform64(n_static * (gw + 1) / nw);
-  while (true) {
-    if (t_begin < t_end) run(t_begin, t_end);
-    if (n_static == n_traces) break;
-    unsigned long long g = 0;
-    if (lane == 0) g = atomicAdd(a.ctr, (unsigned long long)kDynSeg);
-    g = __shfl(g, 0);
-    t_begin = uniform64(n_static + g);
-    if (t_begin >= n_traces) break;
-    t_end = uniform64(t_begin + kDynSeg < n_traces ? t_begin + kDynSeg : n_traces);
-  }
+  walk_traces<kShWaves, 4, Regs>(
+      trace_ptr, n_traces, a.ctr,
+      [&](const Chunk& c, Regs& R) __attribute__((always_inline)) {
+        load_regs(span_id, parent, svcfl, c, lane, R);
+      },
+      [&](const Chunk& c, uint32_t end, uint64_t t0, const Regs& R)
+          __attribute__((always_inline)) { shapes_chunk<SCAN>(wsm, lane, c, end, t0, R, a, off); },
+      // longer than kStage: listed for trace_shapes_big_kernel
+      [&](uint64_t t, uint32_t n) __attribute__((always_inline)) {
+        list_long(a.big, a.big_list, a.big_cap, lane, t, n);
+      });
   for (int o = 32; o > 0; o >>= 1) off += (uint32_t)__shfl_xor((int)off, o);
   if (lane == 0 && off) atomicAdd(a.off_tree, (unsigned long long)off);
 }
 
 // ---- long traces ----------------------------------------------------------
-// Traces and spans of the set that outgrow a chunk: cnt[0] traces, cnt[1]
-// spans (sizes the list and the per-span scratch before the walk).
-__global__ __launch_bounds__(256) void sh_long_count_kernel(const uint64_t* __restrict__ trace_ptr,
-                                                            uint64_t n_traces,
-                                                            unsigned long long* __restrict__ cnt) {
-  unsigned long long nt = 0, ns = 0;
-  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n_traces;
-       t += (uint64_t)gridDim.x * 256) {
-    const uint64_t L = trace_ptr[t + 1] - trace_ptr[t];
-    if (L > (uint64_t)kStage) {
-      nt += 1;
-      ns += L;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    nt += __shfl_xor(nt, o);
-    ns += __shfl_xor(ns, o);
-  }
-  if ((threadIdx.x & 63) == 0 && nt) {
-    atomicAdd(&cnt[0], nt);
-    atomicAdd(&cnt[1], ns);
-  }
-}
-
-// One workgroup per listed trace (tickets, as self_big_kernel).  Parent
-// positions come from that kernel's windowed LDS id table (id -> first
-// position in a window of kBigWin ids, windows probed in trace order).  The
+// One workgroup per listed trace (tickets).  Parent positions come from
+// walk.h's windowed LDS id table (big_parents).  The
 // jump state (H, Mul, ancestor word) lives in global scratch in two buffers:
 // a round reads one and writes the other.  A span's words are written by the
 // thread that owns the span (position % kBigThreads) with agent-scope stores
 // and read by any thread with agent-scope loads, all served by L2; every wave
 // waits for its own stores before the barrier that separates two rounds
-// (sweep_sync, as critical_path.hip).  ceil(log2 L) rounds, fewer when a round
-// finds no open span; then the trace sum by a workgroup reduction.
-constexpr int kBigThreads = 512;
-constexpr int kBigPer = 8;
-constexpr uint32_t kBigWin = 2048;
-constexpr uint32_t kBigSlots = 2 * kBigWin;  // load <= 1/2
-static_assert((kBigSlots & (kBigSlots - 1)) == 0, "power-of-two table");
-
-__device__ __forceinline__ uint32_t big_slot(uint64_t id) {
-  return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32) & (kBigSlots - 1u);
-}
-
-template <typename T>
-__device__ __forceinline__ T aload(const T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ __forceinline__ void astore(T* p, T v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0), expcnt and lgkmcnt at their maxima
-__device__ __forceinline__ void wait_stores() { __builtin_amdgcn_s_waitcnt(kWaitVm0); }
-__device__ __forceinline__ void sweep_sync() {
-  wait_stores();
-  __syncthreads();
-}
-
+// (sweep_sync).  ceil(log2 L) rounds, fewer when a round finds no open span;
+// then the trace sum by a workgroup reduction.
 __global__ __launch_bounds__(kBigThreads) void trace_shapes_big_kernel(
     const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
     const uint32_t* __restrict__ svcfl, const uint64_t* __restrict__ trace_ptr, ShArgs a) {
-  __shared__ unsigned long long bkey[kBigSlots];  // 0 = empty (id 0 is never a parent reference)
-  __shared__ uint32_t bpos[kBigSlots];            // first position in the window
+  __shared__ unsigned long long bkey[kBigSlots];
+  __shared__ uint32_t bpos[kBigSlots];
   __shared__ unsigned long long s_j;
   __shared__ unsigned long long s_sum[kBigThreads / kWave];
   __shared__ unsigned long long s_off[kBigThreads / kWave];
   const int tid = threadIdx.x;
   const uint64_t nbig = a.big[0] < a.big_cap ? a.big[0] : a.big_cap;
-  for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-    bkey[k] = 0ull;
-    bpos[k] = kNone;
-  }
+  big_clear(bkey, bpos, tid);
   while (true) {
     __syncthreads();
     if (tid == 0) s_j = atomicAdd(&a.big[2], 1ull);
@@ -440,53 +290,11 @@ __global__ __launch_bounds__(kBigThreads) void trace_shapes_big_kernel(
     unsigned long long* mB = a.l_m[1] + off;
     uint32_t* wA = a.l_w[0] + off;
     uint32_t* wB = a.l_w[1] + off;
-    // ---- parent positions (self_big_kernel's windows)
+    // ---- parent positions
     for (uint64_t b0 = 0; b0 < L; b0 += kBigThreads * kBigPer) {
       uint64_t pid[kBigPer];
-      uint32_t pp[kBigPer];  // parent position in the trace (kNone: not found yet)
-      bool need = false;
-#pragma unroll
-      for (int r = 0; r < kBigPer; ++r) {
-        const uint64_t i = b0 + (uint64_t)r * kBigThreads + tid;
-        pid[r] = i < L ? parent[lo + i] : 0ull;
-        pp[r] = kNone;
-        need |= pid[r] != 0ull;
-      }
-      for (uint32_t w0 = 0; w0 < L; w0 += kBigWin) {
-        if (!__syncthreads_or(need)) break;  // also orders the previous clear
-        for (uint32_t k = tid; k < kBigWin && (uint64_t)w0 + k < L; k += kBigThreads) {
-          const uint64_t id = span_id[lo + w0 + k];
-          if (id == 0ull) continue;
-          for (uint32_t sl = big_slot(id);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-            const unsigned long long prev = atomicCAS(&bkey[sl], 0ull, (unsigned long long)id);
-            if (prev == 0ull || prev == id) {
-              atomicMin(&bpos[sl], k);  // the first position wins
-              break;
-            }
-          }
-        }
-        __syncthreads();
-        need = false;
-#pragma unroll
-        for (int r = 0; r < kBigPer; ++r) {
-          if (pid[r] == 0ull || pp[r] != kNone) continue;
-          for (uint32_t sl = big_slot(pid[r]);; sl = (sl + 1u) & (kBigSlots - 1u)) {
-            const unsigned long long key = bkey[sl];
-            if (key == pid[r]) {
-              pp[r] = w0 + bpos[sl];
-              break;
-            }
-            if (key == 0ull) break;
-          }
-          need |= pp[r] == kNone;
-        }
-        __syncthreads();
-        for (uint32_t k = tid; k < kBigSlots; k += kBigThreads) {
-          bkey[k] = 0ull;
-          bpos[k] = kNone;
-        }
-        if ((uint64_t)w0 + kBigWin >= L) break;  // (w0 += kBigWin must not wrap)
-      }
+      uint32_t pp[kBigPer];  // parent position in the trace (kNone: none)
+      big_parents(span_id, parent, lo, L, b0, tid, bkey, bpos, pid, pp);
       // The span's starting state.
 #pragma unroll
       for (int r = 0; r < kBigPer; ++r) {
@@ -809,20 +617,10 @@ int anomod_trace_shapes_spans(anomod_ctx* ctx, const anomod_spans* spans,
     if (out->path_hash && n) memset(out->path_hash, 0, n * 8);
     return ANOMOD_OK;
   }
-  // the spans that lie in traces: [trace_ptr[0], trace_ptr[n_traces]) (spans
-  // outside every trace are in no shape: their path_hash reads 0)
-  uint64_t in_traces[2] = {0, 0};
-  if (n) {
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipMemcpyAsync(in_traces + 1, spans->trace_ptr + nt, 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ANOMOD_REQUIRE(ctx, in_traces[0] <= in_traces[1] && in_traces[1] <= n,
-                   "trace_ptr range [%llu, %llu) outside the set's %llu spans",
-                   (unsigned long long)in_traces[0], (unsigned long long)in_traces[1],
-                   (unsigned long long)n);
-  }
+  // the spans that lie in traces (spans outside every trace are in no shape:
+  // their path_hash reads 0)
+  uint64_t in_traces[2];
+  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
   const uint64_t n_in = in_traces[1] - in_traces[0];
   if (n_in == 0) {  // only empty traces: one shape, 0
     uint64_t bad = 0;
@@ -840,43 +638,17 @@ int anomod_trace_shapes_spans(anomod_ctx* ctx, const anomod_spans* spans,
     return ANOMOD_OK;
   }
 
-  // The call's workspace, freed when it returns (after the stream's work): a
-  // block of words (dynamic-tail counter, long-trace counters, off-tree
-  // counter, order-probe scratch, run count) and a block of label keys |
-  // shapes | path hashes (when asked for) | long-trace list | the listed
-  // spans' jump state (40 B per span) | the census arrays (sized to the
+  // The call's workspace: a block of words (dynamic-tail counter, long-trace
+  // counters, off-tree counter, order-probe scratch, run count) and a block of
+  // label keys | shapes | path hashes (when asked for) | long-trace list | the
+  // listed spans' jump state (40 B per span) | the census arrays (sized to the
   // traces).  The long traces are counted first.
-  struct Workspace {
-    anomod_ctx* ctx;
-    void* words = nullptr;
-    void* block = nullptr;
-    ~Workspace() {
-      if (!words && !block) return;
-      (void)hipStreamSynchronize(ctx->stream);
-      if (words) (void)hipFree(words);
-      if (block) (void)hipFree(block);
-    }
-  } ws{ctx};
-  auto take = [&](void** p, size_t bytes) {
-    if (dev_malloc(ctx, p, bytes) == hipSuccess) return ANOMOD_OK;
-    (void)hipGetLastError();
-    *p = nullptr;
-    set_error(ctx, "hipMalloc(%zu) for the trace-shapes workspace failed", bytes);
-    return ANOMOD_ENOMEM;
-  };
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  CallWorkspace ws{ctx};
+  const auto al = CallWorkspace::al;
   unsigned long long nlong[2] = {0ull, 0ull};
-  if (int rc = take(&ws.words, 256)) return rc;
+  if (int rc = ws.take(&ws.words, 256, "trace-shapes")) return rc;
   auto* words = static_cast<unsigned long long*>(ws.words);
-  if (spans->max_trace_len > (uint64_t)kStage) {
-    ANOMOD_HIP(ctx, hipMemsetAsync(words, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(sh_long_count_kernel,
-                       dim3((unsigned)std::min<uint64_t>((nt + 255) / 256, 4ull * ctx->num_cus)),
-                       dim3(256), 0, ctx->stream, spans->trace_ptr, nt, words);
-    ANOMOD_HIP(ctx, hipGetLastError());
-    ANOMOD_HIP(ctx, hipMemcpyAsync(nlong, words, 16, hipMemcpyDeviceToHost, ctx->stream));
-    ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if (int rc = count_long_traces(ctx, spans, words, nlong)) return rc;
   const size_t nl = (size_t)nlong[1];
   const uint64_t m_max = std::min<uint64_t>(out->cap, nt);
   const uint64_t ctiles = (nt + kCTile - 1) / kCTile;
@@ -886,37 +658,33 @@ int anomod_trace_shapes_spans(anomod_ctx* ctx, const anomod_spans* spans,
   const size_t b_sort = radix_temp_bytes(nt), b_t8 = al(nt * 8), b_t4 = al(nt * 4);
   const size_t b_tcnt = al(ctiles * 4), b_cls = out->trace_class ? al(nt) : 0;
   const size_t b_out = al(m_max * 8);
-  if (int rc = take(&ws.block, b_key + b_shape + b_ph + b_list + 4 * b_l8 + 2 * b_l4 + b_sort +
-                                   4 * b_t8 + b_t4 + b_tcnt + b_cls + 4 * b_out))
+  if (int rc = ws.take(&ws.block,
+                       b_key + b_shape + b_ph + b_list + 4 * b_l8 + 2 * b_l4 + b_sort + 4 * b_t8 +
+                           b_t4 + b_tcnt + b_cls + 4 * b_out,
+                       "trace-shapes"))
     return rc;
-  char* wp = static_cast<char*>(ws.block);
-  auto carve = [&](size_t bytes) {
-    char* p = wp;
-    wp += bytes;
-    return p;
-  };
   ShArgs a{};
-  auto* d_key = reinterpret_cast<unsigned long long*>(carve(b_key));
+  auto* d_key = ws.carve<unsigned long long>(b_key);
   a.svc_key = d_key;
-  a.shape = reinterpret_cast<unsigned long long*>(carve(b_shape));
-  a.path_hash = out->path_hash ? reinterpret_cast<unsigned long long*>(carve(b_ph)) : nullptr;
-  a.big_list = reinterpret_cast<unsigned long long*>(carve(b_list));
-  a.l_h[0] = reinterpret_cast<unsigned long long*>(carve(b_l8));
-  a.l_h[1] = reinterpret_cast<unsigned long long*>(carve(b_l8));
-  a.l_m[0] = reinterpret_cast<unsigned long long*>(carve(b_l8));
-  a.l_m[1] = reinterpret_cast<unsigned long long*>(carve(b_l8));
-  a.l_w[0] = reinterpret_cast<uint32_t*>(carve(b_l4));
-  a.l_w[1] = reinterpret_cast<uint32_t*>(carve(b_l4));
-  void* d_sort = carve(b_sort);
-  auto* d_sorted = reinterpret_cast<uint64_t*>(carve(b_t8));  // later the rank keys
-  auto* d_run_val = reinterpret_cast<uint64_t*>(carve(b_t8));
-  auto* d_first = reinterpret_cast<unsigned long long*>(carve(b_t8));
-  auto* d_abn = reinterpret_cast<unsigned long long*>(carve(b_t8));
-  auto* d_run_pos = reinterpret_cast<uint32_t*>(carve(b_t4));
-  auto* d_tcnt = reinterpret_cast<uint32_t*>(carve(b_tcnt));
-  auto* d_cls = out->trace_class ? reinterpret_cast<uint8_t*>(carve(b_cls)) : nullptr;
+  a.shape = ws.carve<unsigned long long>(b_shape);
+  a.path_hash = out->path_hash ? ws.carve<unsigned long long>(b_ph) : nullptr;
+  a.big_list = ws.carve<unsigned long long>(b_list);
+  a.l_h[0] = ws.carve<unsigned long long>(b_l8);
+  a.l_h[1] = ws.carve<unsigned long long>(b_l8);
+  a.l_m[0] = ws.carve<unsigned long long>(b_l8);
+  a.l_m[1] = ws.carve<unsigned long long>(b_l8);
+  a.l_w[0] = ws.carve<uint32_t>(b_l4);
+  a.l_w[1] = ws.carve<uint32_t>(b_l4);
+  void* d_sort = ws.carve(b_sort);
+  auto* d_sorted = ws.carve<uint64_t>(b_t8);  // later the rank keys
+  auto* d_run_val = ws.carve<uint64_t>(b_t8);
+  auto* d_first = ws.carve<unsigned long long>(b_t8);
+  auto* d_abn = ws.carve<unsigned long long>(b_t8);
+  auto* d_run_pos = ws.carve<uint32_t>(b_t4);
+  auto* d_tcnt = ws.carve<uint32_t>(b_tcnt);
+  auto* d_cls = out->trace_class ? ws.carve<uint8_t>(b_cls) : nullptr;
   uint64_t* d_out[4];
-  for (auto& p : d_out) p = reinterpret_cast<uint64_t*>(carve(b_out));
+  for (auto& p : d_out) p = ws.carve<uint64_t>(b_out);
   a.ctr = words;
   a.big = words + 1;
   a.off_tree = words + 6;
@@ -938,23 +706,14 @@ int anomod_trace_shapes_spans(anomod_ctx* ctx, const anomod_spans* spans,
     ANOMOD_HIP(ctx, hipMemcpyAsync(d_cls, out->trace_class, nt, hipMemcpyHostToDevice, ctx->stream));
   ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-  // The scan the edge kernels would use for the set (its order hint is
-  // probed when unknown: the value the first aggregation would find).
-  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
-  bool uni = false;
-  if (int rc = span_scan_choice(ctx, spans, words + 4, &uni)) return rc;
-  const bool long_set = spans->max_trace_len != ~0ull && spans->max_trace_len > (uint64_t)kStage;
-  const int scan = !uni ? kScanFwd : (E > kNarrowRows || long_set) ? kScanSplit : kScanBidir;
+  int scan = kScanFwd;
+  if (int rc = pick_walk_scan(ctx, spans, S, words + 4, &scan)) return rc;
   const WalkFn fn = scan == kScanFwd     ? trace_shapes_kernel<kScanFwd>
                     : scan == kScanSplit ? trace_shapes_kernel<kScanSplit>
                                          : trace_shapes_kernel<kScanBidir>;
-  int per_cu = 0;
-  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                      &per_cu, reinterpret_cast<const void*>(fn), kShThreads, 0));
-  const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
-  if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
-    fprintf(stderr, "anomod: trace-shapes kernel trace_shapes_kernel<%s>, %llu long traces\n",
-            scan == kScanFwd ? "forward" : scan == kScanSplit ? "split" : "bidir", nlong[0]);
+  uint64_t grid = 0;
+  if (int rc = walk_grid(ctx, fn, kShThreads, &grid)) return rc;
+  log_walk_kernel("trace-shapes", "trace_shapes_kernel", scan, nlong[0]);
   ANOMOD_HIP(ctx, hipMemsetAsync(words, 0, 64, ctx->stream));  // every counter
   if (a.path_hash && n_in < n) ANOMOD_HIP(ctx, hipMemsetAsync(a.path_hash, 0, n * 8, ctx->stream));
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kShThreads), 0, ctx->stream, spans->span_id,

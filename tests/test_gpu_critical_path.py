@@ -17,6 +17,7 @@ from critical_path_ref import (FANOUT_SERVICES, T0_US, cp_table_ref, critical_pa
 from self_time_ref import assert_table_equal, parents_ref
 from test_critical_path_host import P_SEQ, synth
 from test_gpu_self_time import _random_tree, _spanset
+from test_gpu_self_time import window_border_case
 
 pytestmark = pytest.mark.gpu
 
@@ -218,6 +219,19 @@ def test_long_and_short_traces_mixed(ctx, monkeypatch, capfd):
     sp.unique_ids = True    # ids are unique; in-trace shuffled: the order probe says forward
     _check(ctx, sp)
     assert ", 8 long traces" in capfd.readouterr().err
+
+
+def test_duplicated_ids_at_window_and_block_borders(ctx, monkeypatch, capfd):
+    """test_gpu_self_time.window_border_case: children of an id carried twice
+    belong to the first carrier, across the lookup's window and block borders."""
+    monkeypatch.setenv("ANOMOD_LOG_KERNEL", "1")
+    sp, want = window_border_case()
+    par = parents_ref(sp)
+    assert all(par[c] == p for c, p in want.items())
+    for made in (random_starts(sp, 9, par), nested_set(sp, par, 0.5, 8)):
+        _, (_, on, _, _) = _check(ctx, made)
+        assert "critical_path_kernel<forward>, 3 long traces" in capfd.readouterr().err
+        assert 0 < on.sum() < sp.n_spans
 
 
 # ------------------------------------------------------------------ arguments

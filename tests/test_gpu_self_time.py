@@ -262,6 +262,62 @@ def test_long_and_short_traces_mixed(ctx, monkeypatch, capfd):
     assert ", 8 long traces" in capfd.readouterr().err
 
 
+def window_border_case(S=9):
+    """Traces of 4097 / 2049 / 300 / 7 spans, not declared unique, for the
+    long-trace parent lookup (windows of 2,048 ids, blocks of 4,096 spans):
+    unique ids with earlier-span parents, unshuffled, then in the 4,097-span
+    trace the same id planted at positions (5, 2050), (2047, 2048) and (4095,
+    4096) — across a window border, on the two sides of one, and on the two
+    sides of the block border — with children of each pair that sit nearer to
+    the later copy: the first copy must win.  The span at 2048 names its own
+    id (its first carrier is 2047, a window earlier), the one at 4096 too (no
+    position follows it: the other child of that pair sits at 100), and span 3
+    of the 2,049-span trace names the id of that trace's position 2048, the
+    only span of its last window.  Returns (span set, {span: parent}), the
+    parents checked against the host model and against the nearest copy."""
+    rng = np.random.default_rng(77)
+    lens = np.array([4097, 2049, 300, 7], np.int64)
+    n = int(lens.sum())
+    starts = np.r_[0, np.cumsum(lens)[:-1]]
+    t_of = np.repeat(np.arange(lens.shape[0]), lens)
+    pos = np.arange(n) - starts[t_of]
+    sid = np.arange(1, n + 1, dtype=np.uint64) + np.uint64(1 << 40)
+    pick = starts[t_of] + (rng.random(n) * np.maximum(pos, 1)).astype(np.int64)
+    pid = np.where(pos > 0, sid[pick], np.uint64(0))
+    for first, later in ((5, 2050), (2047, 2048), (4095, 4096)):
+        sid[later] = sid[first]
+    s1 = int(starts[1])
+    want = {2051: 5, 2049: 2047, 2048: 2047, 4096: 4095, 100: 4095, s1 + 3: s1 + 2048}
+    for child, parent in want.items():
+        pid[child] = sid[parent]
+    pid[4095] = sid[0]              # (span 100 hangs under it: no reference cycle)
+    pid[s1 + 2048] = sid[s1]        # (the same for span 3 of the second trace)
+    sp = _spanset(S, lens, sid, pid, rng.integers(1, 20000, n), rng.integers(0, S, n),
+                  rng.random(n) < 0.1)
+    assert not sp.unique_ids and not sp.check_unique_ids()
+    par = parents_ref(sp)
+    for child, parent in want.items():
+        assert par[child] == parent
+    carriers = {c: np.flatnonzero(sp.span_id[:4097] == sp.parent_span_id[c]) for c in want if c < s1}
+    nearest = {c: int(k[np.argmin(np.abs(k - c) + (k == c) * n)]) for c, k in carriers.items()}
+    assert nearest == {2051: 2050, 2049: 2048, 2048: 2047, 4096: 4095, 100: 4095}
+    assert all(len(k) == 2 and k[0] == want[c] for c, k in carriers.items())
+    return sp, want
+
+
+def test_duplicated_ids_at_window_and_block_borders(ctx, monkeypatch, capfd):
+    monkeypatch.setenv("ANOMOD_LOG_KERNEL", "1")
+    sp, want = window_border_case()
+    _, su = _check(ctx, sp)
+    assert "self_time_kernel<forward>, 3 long traces" in capfd.readouterr().err
+    # span 2047 carries its children's durations, span 2048 none (the model's
+    # sums, spelled out for the pair on the two sides of a window border)
+    kids = [c for c, p in enumerate(parents_ref(sp)) if p == 2047]
+    assert {2048, 2049} <= set(kids) and not (parents_ref(sp) == 2048).any()
+    assert su[2048] == sp.dur_us[2048]
+    assert su[2047] == max(0, int(sp.dur_us[2047]) - int(sp.dur_us[kids].astype(np.int64).sum()))
+
+
 def test_long_topology(ctx, monkeypatch, capfd):
     """SynthSpec("LONG"): unique ids, traces beyond a chunk; the long-trace
     kernel ran."""

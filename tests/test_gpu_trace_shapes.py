@@ -14,6 +14,8 @@ from anomod.engine import Experiment
 from trace_shapes_ref import (B, M64, SEED_ROOT, census_ref, chain, from_trees, mix64,
                               novelty_ref, path_hash_ref, random_tree, service_keys, shapes_ref,
                               shuffled, spanset, without_subtrees)
+from trace_shapes_ref import label_keys
+from test_gpu_self_time import window_border_case
 
 pytestmark = pytest.mark.gpu
 
@@ -215,6 +217,23 @@ def test_duplicated_ids(ctx):
     assert not sp.check_unique_ids()
     got = _check(ctx, sp)
     assert got.off_tree_spans > 0          # some overwrites close reference cycles
+
+
+def test_duplicated_ids_at_window_and_block_borders(ctx, monkeypatch, capfd):
+    """test_gpu_self_time.window_border_case: children of an id carried twice
+    belong to the first carrier, across the lookup's window and block borders;
+    every span of the case is on its tree."""
+    monkeypatch.setenv("ANOMOD_LOG_KERNEL", "1")
+    sp, want = window_border_case()
+    got = _check(ctx, sp, use_errors=True)
+    assert "trace_shapes_kernel<forward>, 3 long traces" in capfd.readouterr().err
+    assert got.off_tree_spans == 0
+    # span 2049 continues the path of span 2047, the first carrier of its
+    # parent id, not that of span 2048, the later one
+    K = label_keys(sp, use_errors=True)[2049]
+    assert want[2049] == 2047
+    assert int(got.path_hash[2049]) == (int(got.path_hash[2047]) * B + K) & M64
+    assert int(got.path_hash[2049]) != (int(got.path_hash[2048]) * B + K) & M64
 
 
 def test_empty_traces_and_no_spans(ctx):
