@@ -1,6 +1,6 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
                                  [--spectrum] [--critical-path] [--shapes]
-                                 [--baseline <trace file|dir>]
+                                 [--error-origins] [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
 Computes the RCA features of one experiment on the GPU and writes them as JSON:
@@ -40,6 +40,20 @@ def shapes_doc(census, spans, base=None, top: int = 20) -> dict:
             "top": rows}
 
 
+def error_origins_doc(eo) -> dict:
+    """The "error_origins" object of the features JSON: per service the
+    failures that started in it (origin), the error spans that relayed a
+    callee's failure (propagated), the origins that reached their trace's
+    entry (surfaced) and the mean hops of the origins; error_spans and
+    loop_spans of the whole set."""
+    org, prop = eo.per_service("origin"), eo.per_service("propagated")
+    surf, hops = eo.per_service("surfaced"), eo.mean_hops()
+    return {"error_spans": int(eo.error_spans), "loop_spans": int(eo.loop_spans),
+            "services": {s: {"origin": int(org[i]), "propagated": int(prop[i]),
+                             "surfaced": int(surf[i]), "mean_hops": float(hops[i])}
+                         for i, s in enumerate(eo.services)}}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m anomod")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -68,6 +82,10 @@ def main(argv=None) -> int:
                    help="also take the trace shape census (the distinct call trees of the run "
                         "and how many traces have each; against --baseline, which shapes are "
                         "new) and write it as \"shapes\"")
+    f.add_argument("--error-origins", action="store_true",
+                   help="also tell the error-flagged spans whose failure started there from "
+                        "those that relayed a callee's failure, score services by the failures "
+                        "that started in them, and write the counts as \"error_origins\"")
     f.add_argument("--baseline", metavar="TRACES",
                    help="trace file (or dir) of a normal run: its features are the baseline "
                         "of the latency term and of the spectrum's latency thresholds")
@@ -90,7 +108,7 @@ def main(argv=None) -> int:
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
                      critical_path=args.critical_path, trace_quantile=args.trace_quantile,
-                     shapes=args.shapes)
+                     shapes=args.shapes, error_origins=args.error_origins)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -124,6 +142,9 @@ def main(argv=None) -> int:
     if feats.shapes is not None:
         doc["shapes"] = shapes_doc(feats.shapes, exp.spans,
                                    baseline.shapes if baseline is not None else None)
+    if feats.error_origins is not None:
+        doc["error_origins"] = error_origins_doc(feats.error_origins)
+        doc["loop_spans"] = int(feats.error_origins.loop_spans)
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

@@ -131,6 +131,23 @@ class TraceShapesC(C.Structure):
     ]
 
 
+class ErrorOriginsC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("error_spans", C.c_uint64),
+        ("loop_spans", C.c_uint64),
+        ("origin", C.POINTER(C.c_uint64)),
+        ("propagated", C.POINTER(C.c_uint64)),
+        ("stopped", C.POINTER(C.c_uint64)),
+        ("surfaced", C.POINTER(C.c_uint64)),
+        ("absorbers", C.POINTER(C.c_uint64)),
+        ("hops_sum", C.POINTER(C.c_uint64)),
+        ("hops_max", C.POINTER(C.c_uint32)),
+        ("span_state", C.POINTER(C.c_uint8)),
+        ("span_hops", C.POINTER(C.c_uint32)),
+    ]
+
+
 class TraceStructC(C.Structure):
     _fields_ = [
         ("n_services", C.c_uint32),
@@ -249,6 +266,7 @@ _SIGS = {
                                                _P(C.c_uint8)]),
     "anomod_trace_spectrum_spans": (_i32, [_vp, _vp, _P(TraceSpectrumC)]),
     "anomod_trace_shapes_spans": (_i32, [_vp, _vp, _P(TraceShapesC)]),
+    "anomod_error_origins_spans": (_i32, [_vp, _vp, _P(ErrorOriginsC)]),
     "anomod_edge_aggregate_host": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _u32, _i32,
                                           _P(_i32), _P(_i32), _P(EdgeTableC)]),
     "anomod_edge_aggregate": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _P(EdgeTableC)]),

@@ -11,8 +11,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import (CriticalPath, EdgeTable, EdgeWindows, SpanSet, TraceShapes, TraceSpectrum,
-                    TraceStructure, edge_rows)
+from .spans import (CriticalPath, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
+                    TraceSpectrum, TraceStructure, edge_rows)
 
 
 @dataclass
@@ -627,6 +627,31 @@ class Context:
             k = min(m, int(cs.n_shapes))
             return TraceShapes(list(spans.services), *(a[:k] for a in arrs), int(cs.n_shapes),
                                int(cs.off_tree_spans), tshape, phash, bool(use_errors))
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def error_origins(self, spans: DeviceSpans | SpanSet, per_span: bool = False) -> ErrorOrigins:
+        """Error origins of a grouped set (anomod_error_origins_spans): per
+        edge row the error-flagged spans whose failure started there (origin)
+        or passed through (propagated), where failures were stopped, how many
+        reached their trace's entry (surfaced), the spans that absorbed a
+        callee's failure and the hops the failures travelled.  per_span=True
+        also returns span_state (class | fate << 2) and span_hops by span
+        position.  Rank-local.  A host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            tmp = spans = self.upload(spans)
+        try:
+            eo = ErrorOrigins.empty(spans.services, int(spans.n_spans) if per_span else None)
+            cs = L.ErrorOriginsC(len(spans.services), 0, 0,
+                                 *(L.ptr(getattr(eo, k), C.c_uint64) for k in eo.TABLES[:6]),
+                                 L.ptr(eo.hops_max, C.c_uint32), L.ptr(eo.span_state, C.c_uint8),
+                                 L.ptr(eo.span_hops, C.c_uint32))
+            self._check(self._lib.anomod_error_origins_spans(self.handle, spans.handle,
+                                                             C.byref(cs)))
+            eo.error_spans, eo.loop_spans = int(cs.error_spans), int(cs.loop_spans)
+            return eo
         finally:
             if tmp is not None:
                 tmp.free()

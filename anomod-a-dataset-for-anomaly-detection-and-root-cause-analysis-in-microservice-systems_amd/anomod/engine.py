@@ -23,8 +23,8 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import (EdgeTable, EdgeWindows, SpanSet, TraceShapes, TraceSpectrum, edge_rows,
-                    spectrum_thresholds)
+from .spans import (EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes, TraceSpectrum,
+                    edge_rows, spectrum_thresholds)
 
 # --------------------------------------------------------------------------
 # Ground-truth labels (experiment name -> faulty service), SURVEY.md §2:
@@ -174,6 +174,8 @@ class Features:
     cp_edges: EdgeTable | None = None
     # features(shapes=True): the trace shape census
     shapes: TraceShapes | None = None
+    # features(error_origins=True): where failures started and how far they travelled
+    error_origins: ErrorOrigins | None = None
 
 
 _default_ctx: Context | None = None
@@ -287,7 +289,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              trace_W: int = 6, trace_eps: float = 1e-2, trace_min_count: int = 5,
              self_time: bool = False, spectrum: bool = False,
              spectrum_rows: str = "root", critical_path: bool = False,
-             trace_quantile: int | None = None, shapes: bool = False) -> Features:
+             trace_quantile: int | None = None, shapes: bool = False,
+             error_origins: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -316,7 +319,13 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     is on), and against a baseline that has one the score gains 0.25 * the
     shape novelty (TraceShapes.novelty: per service, the share of the traces
     — among those whose shape's exemplar holds the service — whose shape the
-    baseline run does not have; components["shape_novelty"])."""
+    baseline run does not have; components["shape_novelty"]).  With
+    error_origins the result also holds the error origins
+    (Context.error_origins) and the score's error term is the origin rate —
+    the failures that started in a service over the spans it served — instead
+    of the inclusive error rate, which also fires for every caller that merely
+    relayed a callee's failure: components["error_rate"] then holds the origin
+    rate and components["error_kind"] is "origin".  No baseline is involved."""
     if trace_quantile is not None and trace_step_s is None:
         raise ValueError("features(trace_quantile=...) needs trace_step_s")
     if trace_quantile is not None and not 0 <= int(trace_quantile) <= 99:
@@ -356,6 +365,10 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     cnt = edges.count.reshape(S + 2, S).sum(axis=0).astype(np.float64)
     err = edges.errors.reshape(S + 2, S).sum(axis=0).astype(np.float64)
     err_rate = np.divide(err, cnt, out=np.zeros(S), where=cnt > 0)
+    origins = None
+    if error_origins:
+        origins = ctx.error_origins(exp.spans)
+        err_rate = origins.origin_rate(edges.count)
     lat = np.zeros(S)
     use_self = self_edges is not None and baseline is not None and baseline.self_edges is not None
     use_cp = cp_edges is not None and baseline is not None and baseline.cp_edges is not None
@@ -372,6 +385,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     if self_time or critical_path:
         params["components"]["latency_kind"] = ("critical" if use_cp else
                                                 "self" if use_self else "inclusive")
+    if error_origins:
+        params["components"]["error_kind"] = "origin"
     spec = None
     if spectrum:
         thr = (spectrum_thresholds(baseline.edges, edges.services, rows=spectrum_rows)
@@ -391,7 +406,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
             score = score + 0.25 * nov
     if trace_step_s is None:
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
-                        spectrum=spec, cp_edges=cp_edges, shapes=census)
+                        spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count,
                              trace_quantile)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
@@ -402,7 +417,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         params["trace_quantile"] = int(trace_quantile)
     return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
-                    spectrum=spec, cp_edges=cp_edges, shapes=census)
+                    spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

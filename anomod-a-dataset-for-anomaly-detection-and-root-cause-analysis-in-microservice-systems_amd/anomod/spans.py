@@ -434,6 +434,83 @@ class TraceShapes:
         return np.divide(num, den, out=np.zeros(holds.shape[1]), where=den > 0)
 
 
+ERR_CLEAN, ERR_ORIGIN, ERR_PROPAGATED, ERR_ABSORBER = 0, 1, 2, 3
+FATE_SURFACED, FATE_CONTAINED, FATE_LOOP = 1, 2, 3
+
+
+@dataclass
+class ErrorOrigins:
+    """Error origins of a span set (anomod_error_origins_spans): every
+    error-flagged span is the place its failure started (ORIGIN: no failing
+    callee) or a place it passed through (PROPAGATED), a span without the flag
+    whose callee failed is an ABSORBER; a failure follows its chain of failing
+    callers and is SURFACED (the chain ends at a trace head), CONTAINED (it
+    ends below a caller that did not fail) or in a LOOP (a reference cycle).
+    Rows as in EdgeTable; origin + propagated equals EdgeTable.errors."""
+
+    services: list[str]
+    origin: np.ndarray                # u64 [E] ORIGIN spans
+    propagated: np.ndarray            # u64 [E] PROPAGATED spans
+    stopped: np.ndarray               # u64 [E] error spans at the top of a CONTAINED chain
+    surfaced: np.ndarray              # u64 [E] ORIGIN spans of fate SURFACED
+    absorbers: np.ndarray             # u64 [E] ABSORBER spans
+    hops_sum: np.ndarray              # u64 [E] hops of the ORIGIN spans
+    hops_max: np.ndarray              # u32 [E] (0 for a row without an ORIGIN span)
+    error_spans: int = 0              # error-flagged spans in traces
+    loop_spans: int = 0               # those of fate LOOP
+    span_state: np.ndarray | None = None  # u8 [n_spans] class | fate << 2 (per_span=True)
+    span_hops: np.ndarray | None = None   # u32 [n_spans] (per_span=True)
+
+    TABLES = ("origin", "propagated", "stopped", "surfaced", "absorbers", "hops_sum", "hops_max")
+
+    @staticmethod
+    def empty(services: list[str], n_spans: int | None = None) -> "ErrorOrigins":
+        """Zeroed tables over `services`; n_spans: also the per-span columns."""
+        E = edge_rows(len(services))
+        return ErrorOrigins(list(services), *(np.zeros(E, np.uint64) for _ in range(6)),
+                            np.zeros(E, np.uint32), 0, 0,
+                            None if n_spans is None else np.zeros(n_spans, np.uint8),
+                            None if n_spans is None else np.zeros(n_spans, np.uint32))
+
+    def per_service(self, name: str) -> np.ndarray:
+        """A table summed over the parent rows: one value per child service
+        (the maximum for hops_max)."""
+        S = len(self.services)
+        t = getattr(self, name).reshape(S + 2, S)
+        return t.max(axis=0) if name == "hops_max" else t.sum(axis=0)
+
+    def origin_rate(self, count: np.ndarray) -> np.ndarray:
+        """Per service: the failures that started in it over the spans it
+        served — origin summed over the parent rows, divided by the service's
+        span count (count: u64 [E] as EdgeTable.count, or [S] per service); 0
+        where the count is 0."""
+        S = len(self.services)
+        cnt = np.asarray(count)
+        if cnt.shape == (edge_rows(S),):
+            cnt = cnt.reshape(S + 2, S).sum(axis=0)
+        elif cnt.shape != (S,):
+            raise ValueError(f"count has shape {cnt.shape}, expected ({edge_rows(S)},) or ({S},)")
+        cnt = cnt.astype(np.float64)
+        return np.divide(self.per_service("origin").astype(np.float64), cnt, out=np.zeros(S),
+                         where=cnt > 0)
+
+    def surfaced_share(self) -> np.ndarray:
+        """Per service: the share of the failures that started in it and
+        reached their trace's entry (surfaced / origin); 0 where origin is 0."""
+        S = len(self.services)
+        org = self.per_service("origin").astype(np.float64)
+        return np.divide(self.per_service("surfaced").astype(np.float64), org, out=np.zeros(S),
+                         where=org > 0)
+
+    def mean_hops(self) -> np.ndarray:
+        """Per service: the mean number of failing callers above a failure that
+        started in it (hops_sum / origin); 0 where origin is 0."""
+        S = len(self.services)
+        org = self.per_service("origin").astype(np.float64)
+        return np.divide(self.per_service("hops_sum").astype(np.float64), org, out=np.zeros(S),
+                         where=org > 0)
+
+
 def spectrum_thresholds(base: EdgeTable, services: list[str], *, rows: str = "root",
                         min_count: int = 10) -> np.ndarray:
     """Latency thresholds (u32 [E] over `services`) for Context.trace_spectrum

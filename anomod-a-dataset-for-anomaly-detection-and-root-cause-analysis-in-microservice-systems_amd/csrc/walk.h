@@ -1,5 +1,5 @@
 // What the span-walk passes (self time, critical path, trace shapes, trace
-// spectrum) share around chunk.h's leaves: the parent-scan dispatch, the
+// spectrum, error origins) share around chunk.h's leaves: the parent-scan dispatch, the
 // pipelined walk driver with its share policy, the listing of traces longer
 // than a chunk and their windowed parent lookup, the sweep barrier of the
 // long-trace kernels, and the host side of a call (trace range, workspace,

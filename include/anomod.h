@@ -568,6 +568,67 @@ typedef struct {
 } anomod_trace_shapes;
 int anomod_trace_shapes_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               anomod_trace_shapes* out);
+/* Error origins of a grouped set: where failures start, how far they travel
+ * up their callers and whether they reach the trace's entry.  Collectors mark
+ * a failing leaf and every caller that failed because of it alike; this call
+ * tells them apart.  With err(i) = flags[i] & ANOMOD_FLAG_ERROR, par(i) the
+ * parent rule of the self-time call (a ROOT, an ORPHAN and a SELF reference
+ * have no parent and are heads; duplicated ids resolve to the first carrier),
+ * row(i) the edge row of anomod_edge_aggregate_spans and kid_err(j) the
+ * number of error-flagged spans whose parent is j:
+ *   class(i) = ANOMOD_ERR_CLEAN       !err(i) && kid_err(i) == 0
+ *              ANOMOD_ERR_ORIGIN       err(i) && kid_err(i) == 0
+ *              ANOMOD_ERR_PROPAGATED   err(i) && kid_err(i) >  0
+ *              ANOMOD_ERR_ABSORBER    !err(i) && kid_err(i) >  0
+ * The chain of an error-flagged span follows up(i) = par(i) while that
+ * parent exists and carries the flag; hops(i) counts the steps to the span
+ * without an up, top(i), and
+ *   fate(i)  = ANOMOD_FATE_SURFACED   top(i) is a head
+ *              ANOMOD_FATE_CONTAINED  top(i) has a parent (which carries no flag)
+ *              ANOMOD_FATE_LOOP       the chain never ends: a reference cycle of
+ *                                     two or more error-flagged spans, or a span
+ *                                     hanging off one; hops(i) = 0
+ * (a SELF reference is a head, so a one-span cycle is no loop); a span
+ * without the flag has fate 0 and hops 0.  Per edge row, over the spans of
+ * the row that lie in traces: origin / propagated count the spans of those
+ * classes (origin + propagated equals the edge table's errors, row by row),
+ * stopped the error-flagged spans with hops 0 and fate CONTAINED (the edge on
+ * which a failure was stopped), surfaced the ORIGIN spans of fate SURFACED,
+ * absorbers the ABSORBER spans, hops_sum / hops_max the hops of the ORIGIN
+ * spans (hops_max 0 for a row without one).  error_spans counts the
+ * error-flagged spans in traces, loop_spans those of fate LOOP.  span_state[i]
+ * = class | fate << 2 and span_hops[i] by span position; spans outside every
+ * trace read 0 / 0 and are not counted.  Every result is an integer, bit-exact
+ * for any launch geometry.  NULL outputs are skipped; n == 0 gives zeros; an
+ * ungrouped set is ANOMOD_ESTATE; a service index >= n_services is
+ * ANOMOD_EINVAL; at most 2^32 - 2 spans per call.  The call is rank-local: no
+ * collective runs even with a communicator attached (a caller sums the ranks'
+ * tables itself, taking the maximum for hops_max).  The set's histogram-form
+ * hint is neither read nor changed; an unknown order hint is probed as in the
+ * self-time call.                                                           */
+#define ANOMOD_ERR_CLEAN 0u
+#define ANOMOD_ERR_ORIGIN 1u
+#define ANOMOD_ERR_PROPAGATED 2u
+#define ANOMOD_ERR_ABSORBER 3u
+#define ANOMOD_FATE_SURFACED 1u
+#define ANOMOD_FATE_CONTAINED 2u
+#define ANOMOD_FATE_LOOP 3u
+typedef struct {
+  uint32_t n_services;   /* in : S; E = (S + 2) * S as in anomod_edge_table      */
+  uint64_t error_spans;  /* out                                                  */
+  uint64_t loop_spans;   /* out                                                  */
+  uint64_t* origin;      /* [E] host; each array may be NULL                     */
+  uint64_t* propagated;  /* [E]                                                  */
+  uint64_t* stopped;     /* [E]                                                  */
+  uint64_t* surfaced;    /* [E]                                                  */
+  uint64_t* absorbers;   /* [E]                                                  */
+  uint64_t* hops_sum;    /* [E]                                                  */
+  uint32_t* hops_max;    /* [E]                                                  */
+  uint8_t* span_state;   /* [n_spans] host, may be NULL                          */
+  uint32_t* span_hops;   /* [n_spans] host, may be NULL                          */
+} anomod_error_origins;
+int anomod_error_origins_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                               anomod_error_origins* out);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
