@@ -22,6 +22,22 @@
 // lives in HBM between calls so an arbitrarily long T is streamed in chunks
 // (400 GB at 10^6 x 10^5 does not fit 288 GB of HBM).  HBM-bound: 4 B/sample
 // read + 4/W B/sample written.
+//
+// Input domain.  The state is f64 but a score is formed in f32,
+// z = (float)d * rsq((float)v + eps) (zscale below), which sets two limits:
+//  * samples: |x| <= 2^62 (or NaN = missing).  Then |d| <= 2^63 and v <= d^2
+//    <= 2^126 < FLT_MAX, so both conversions stay finite.  Beyond it nothing
+//    is checked: once v > FLT_MAX, (float)v is inf and the series scores 0
+//    (finite * rsq(inf) = 0); |d| > FLT_MAX scores inf.  A +-inf sample makes
+//    the state, and every later score of that series, non-finite.
+//  * eps >= 2^-126 (FLT_MIN), enforced by anomod_series_ewma_z (EINVAL).  The
+//    hardware reciprocal square root takes a denormal argument as 0: with
+//    eps = 0 or 1e-40 a series of magnitude 1e-21 (v ~ 1e-42, an f32
+//    denormal) scored inf in every window where the exact score is O(1).
+//    With eps >= 2^-126 the sum (float)v + eps is a normal f32 whatever v is.
+// Inside the domain every score is within 5 * 2^-24 |z| + 4 * 2^-53 / alpha *
+// max|x| / sqrt(v + eps) of the exact recurrence (tests/ewma_ref.py).
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 
@@ -53,9 +69,10 @@ struct EwmaState {
   uint32_t n;
 };
 
-// 1/sqrt(v + eps) with the hardware reciprocal square root (v_rsq_f32, 1 ulp):
-// v + eps is never denormal for eps >= 2^-126, so rsqrtf's denormal rescaling
-// is dead weight on the recurrence's critical path.
+// 1/sqrt(v + eps) with the hardware reciprocal square root (v_rsq_f32, 1 ulp).
+// It reads a denormal argument as 0 (-> inf); the entry point requires eps >=
+// 2^-126, so (float)v + eps is a normal f32 and rsqrtf's denormal rescaling
+// would be dead weight on the recurrence's critical path.
 __device__ __forceinline__ float zscale(double v, float eps) {
   return __builtin_amdgcn_rsqf((float)v + eps);
 }
@@ -774,7 +791,11 @@ int anomod_series_ewma_z(anomod_ctx* ctx, anomod_series* ser, float alpha, uint3
   ANOMOD_REQUIRE(ctx, W >= 1 && ser->T % W == 0, "T=%llu must be a multiple of W=%u",
                  (unsigned long long)ser->T, W);
   ANOMOD_REQUIRE(ctx, alpha > 0.f && alpha <= 1.f, "alpha=%g outside (0, 1]", (double)alpha);
-  ANOMOD_REQUIRE(ctx, eps >= 0.f, "eps must be >= 0");
+  // zscale's precondition (a NaN eps fails the comparison too)
+  ANOMOD_REQUIRE(ctx, eps >= FLT_MIN,
+                 "eps=%g must be >= 2^-126 (%g): v + eps has to be a normal f32 for the "
+                 "reciprocal square root",
+                 (double)eps, (double)FLT_MIN);
   if (int rc = bind(ctx)) return rc;
   const uint64_t nw = ser->T / W;
   const size_t zbytes = nw * ser->S * 4;

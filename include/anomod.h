@@ -746,7 +746,11 @@ int anomod_response_summary(anomod_ctx* ctx, const uint32_t* status_id, const ui
  * with m = x, v = 0, z = 0 at the first valid sample; NaN samples leave the
  * state untouched and score 0.  Z[w][s] = max |z_t| over t in window w of W
  * steps (T must be a multiple of W).  m/v equal pandas
- * Series.ewm(alpha, adjust=False).mean() / .var(bias=True).  The metric
+ * Series.ewm(alpha, adjust=False).mean() / .var(bias=True).  alpha in (0, 1];
+ * eps >= 2^-126 (FLT_MIN; smaller, 0 included, is ANOMOD_EINVAL: the f32
+ * reciprocal square root needs a normal v + eps).  Samples are |x| <= 2^62
+ * or NaN; beyond that nothing is checked and a series whose variance leaves
+ * the f32 range scores 0.  The metric
  * matrix replaces the long CSV rows of metric_collector.py:427-443 and
  * fetch_prometheus_metrics.py:53-67.                                       */
 int anomod_ewma_z(anomod_ctx* ctx, const float* X, uint64_t T, uint64_t S, float alpha,
