@@ -247,6 +247,7 @@ _SIGS = {
     "anomod_spans_hist_compact": (_i32, [_vp, _P(C.c_int)]),
     "anomod_spans_hints": (_i32, [_vp, _P(C.c_int), _P(C.c_int)]),
     "anomod_spans_set_hints": (_i32, [_vp, C.c_int, C.c_int]),
+    "anomod_spans_parent_rows": (_i32, [_vp, _vp, _P(C.c_uint16), _u32]),
     "anomod_spans_upload_ungrouped": (_i32, [_vp, _P(SpanSoA), _u64, _P(_vp)]),
     "anomod_spans_grouped": (_i32, [_vp, _P(_i32)]),
     "anomod_spans_group": (_i32, [_vp, _vp, _P(_vp)]),

@@ -128,6 +128,21 @@ struct anomod_spans {
   uint32_t* dur_us = nullptr;
   uint64_t* trace_ptr = nullptr;  // [n_traces + 1]
   uint64_t* start_us = nullptr;   // [n_spans] epoch microseconds, or none (edge_windows.hip)
+  // Parent rows (edge_agg.hip): the service row of every span's first-match
+  // parent, by span position, for the spans inside [rows_lo, rows_hi) =
+  // [trace_ptr[0], trace_ptr[n_traces]) — rows_S for a root span, rows_S + 1
+  // for an orphan, rows_S = the service count of the aggregation that filled
+  // it (a reader with another S maps them to its own S / S + 1; service
+  // indices stay below both).  Filled by the set's first grouped aggregation
+  // (the id columns and trace_ptr of a resident set never change), complete
+  // once rows_done; later aggregations stream svc_flags, dur_us and this
+  // column instead of walking the traces.  Allocated on demand (2 B/span); a
+  // set that lives for one call (keep_rows = false) never gets one.
+  mutable uint16_t* parent_row = nullptr;  // [n_spans]
+  mutable bool rows_done = false;
+  mutable uint32_t rows_S = 0;
+  mutable uint64_t rows_lo = 0, rows_hi = 0;
+  bool keep_rows = true;
 };
 
 #define ANOMOD_HIP(ctx, expr)                                                               \
@@ -234,8 +249,10 @@ int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uin
 // the ctx stream.  ws: device words the walk uses, span_edge_keys_ws_bytes
 // of them, 8-B aligned.
 size_t span_edge_keys_ws_bytes(const anomod_spans* s);
+// use_rows: a set that holds its parent rows (anomod_spans::parent_row) gets
+// the keys from the row stream instead (the exact edge quantiles).
 int span_edge_keys(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, unsigned long long* keys,
-                   unsigned long long* ws);
+                   unsigned long long* ws, bool use_rows = false);
 // The parent scan the edge kernels use for a grouped set (edge_agg.hip):
 // *unique = the scans from both ends apply (ids declared unique, collector
 // order).  An unknown order hint is probed first, as at the set's first

@@ -33,7 +33,11 @@
 //    with u64 atomics;
 //  * per-edge error/sum/min/max live in LDS (E <= 512) and are flushed once;
 //  * all merges are integer adds / min / max: results are bit-exact and
-//    independent of geometry, scheduling and shard count.
+//    independent of geometry, scheduling and shard count;
+//  * a resident set is walked once: its first aggregation also stores every
+//    span's parent row (u16, anomod_spans::parent_row), and its later ones
+//    stream svc_flags + dur_us + the row, 10 B/span, into the same tables
+//    (edge_row_kernel) — no ids, no trace bounds, no scan.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -125,7 +129,9 @@ struct Table {
   unsigned long long* big;       // long traces: [0] listed, [1] / [2] tickets of the
                                  // resolve / record kernels
   unsigned long long* big_list;  // long traces: trace indices
-  uint16_t* bpar;            // long traces: every listed span's parent row (S root, S + 1 orphan)
+  uint16_t* bpar;            // parent rows by span position (S root, S + 1 orphan): call scratch
+                             // the long-trace pass fills for its listed spans, or the set's
+                             // parent-row column, which the chunk walk (ROWS) fills too
   uint64_t t_base;           // trace index of this launch's first trace
   unsigned long long* ovf;   // [0] spans whose pair-form probe chain was full (counted in
                              // HBM), [1] workgroups that stopped at a saturated pair table
@@ -403,17 +409,24 @@ __device__ __forceinline__ void load_regs(const Cols& col, const Chunk& c, int l
 // trace_collector.py:424-443).
 constexpr uint32_t kScan = 10;  // ids compared per step (kScan / 2 x ds_read2_b64)
 static_assert(kScan % 2 == 0 && kScan <= 16, "scan step");
+// The forward scan's step in the compact-form instantiations that also store
+// parent rows (process_chunk ROWS): those forms sit at the 128-register limit
+// with kScan, and the row store's scalar descriptor pushed them over it (1-2
+// spilled registers); 8 ids per step fits.  They run once per set.
+constexpr uint32_t kScanRows = 8;
 
+template <uint32_t SCAN = kScan>
 __device__ __forceinline__ int find_parent(const uint64_t* lsid, uint32_t a, uint32_t b,
                                            uint64_t pid) {
-  for (uint32_t q0 = a; q0 < b; q0 += kScan) {
-    uint64_t v[kScan];
+  static_assert(SCAN % 2 == 0 && SCAN <= chunk::kScanSlack, "scan step");
+  for (uint32_t q0 = a; q0 < b; q0 += SCAN) {
+    uint64_t v[SCAN];
 #pragma unroll
-    for (uint32_t j = 0; j < kScan; ++j) v[j] = lsid[q0 + j];
+    for (uint32_t j = 0; j < SCAN; ++j) v[j] = lsid[q0 + j];
     uint32_t m = 0;
 #pragma unroll
-    for (uint32_t j = 0; j < kScan; ++j) m |= (v[j] == pid ? 1u : 0u) << j;
-    const uint32_t hi = (b - q0) < kScan ? (b - q0) : kScan;  // >= 1
+    for (uint32_t j = 0; j < SCAN; ++j) m |= (v[j] == pid ? 1u : 0u) << j;
+    const uint32_t hi = (b - q0) < SCAN ? (b - q0) : SCAN;  // >= 1
     m &= (1u << hi) - 1u;
     if (m) return (int)(q0 + __ffs(m) - 1u);
   }
@@ -435,7 +448,11 @@ __device__ __forceinline__ int find_parent(const uint64_t* lsid, uint32_t a, uin
 // and keeps the mask form over u64 ids at (kFwd, kBwd).
 constexpr uint32_t kLFwd = 12, kLBwd = 4;  // the long-trace sets' widths
 constexpr uint32_t kWFwd = 12, kWBwd = 4;  // TrainTicket width, split scan
-template <int HT, int ST, bool UNI, bool WIDE = false>
+// ROWS: also store every span's parent row into the set's parent-row column
+// (tab.bpar, by span position): one buffer store per span row through a
+// descriptor on the chunk's part of the column, with the lane offsets of the
+// loads (lanes past the chunk are dropped by the descriptor's bound).
+template <int HT, int ST, bool UNI, bool WIDE = false, bool ROWS = false>
 __device__ __forceinline__ void process_chunk(unsigned char* smem, unsigned char* wsm, int lane,
                                               const Chunk& c, const Regs& R, uint32_t S,
                                               const Table& tab) {
@@ -487,12 +504,16 @@ __device__ __forceinline__ void process_chunk(unsigned char* smem, unsigned char
           q = find_parent_split<kWFwd, kWBwd>(llo, lhi, a, b, i, R.pid[r]);
         else
           q = UNI ? find_parent_bidir<kFwd, kBwd>(lsid, a, b, i, R.pid[r])
-                  : find_parent(lsid, a, b, R.pid[r]);
+                  : find_parent<(ROWS && HT == kHtCompact) ? kScanRows : kScan>(lsid, a, b,
+                                                                                 R.pid[r]);
         if (q >= 0) p = lsvc[q];
       } else {  // ablation: a parent-like edge without the lookup (keeps key diversity)
         p = ((R.sf[r] & 0xFFFFu) + 1u + (uint32_t)(R.pid[r] & 1u)) % S;
       }
     }
+    if constexpr (ROWS)
+      __builtin_amdgcn_raw_buffer_store_b16((short)p, rsrc(tab.bpar + c.base, c.n * 2u),
+                                            (int)(i * 2u), 0, 0);
     if constexpr (HT == kHtKeys) {
       if (i < c.n)
         tab.keys[c.base + i] = ((unsigned long long)(p * S + (R.sf[r] & 0xFFFFu)) << 32) | R.dur[r];
@@ -992,7 +1013,7 @@ __global__ __launch_bounds__(kBigThreads) void edge_big_record_kernel(
   tables_flush<HT, ST>(smem, E, tab, tid);
 }
 
-template <int HT, int ST, bool UNI, int MODE = kModeNormal>
+template <int HT, int ST, bool UNI, int MODE = kModeNormal, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void edge_agg_kernel(
     const uint64_t* __restrict__ span_id, const uint64_t* __restrict__ parent,
     const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
@@ -1088,7 +1109,7 @@ __global__ __launch_bounds__(kThreads) void edge_agg_kernel(
           tab.big_list[atomicAdd(&tab.big[0], 1ull)] =
               tab.t_base + (MODE == kModeAuto ? *wt_cur : t_cur);
       } else {
-        process_chunk<HT, ST, UNI, MODE == kModeWideScan>(smem, wsm, lane, cur, R, S, tab);
+        process_chunk<HT, ST, UNI, MODE == kModeWideScan, ROWS>(smem, wsm, lane, cur, R, S, tab);
       }
       if (!has_next) break;
       cur = nxt;
@@ -1149,6 +1170,91 @@ __global__ __launch_bounds__(kThreads) void edge_rec_kernel(const uint64_t* __re
   }
   __syncthreads();
   tables_flush<HT, ST>(smem, E, tab, tid);  // (the caller sets tab.occupancy)
+}
+
+// A set whose parent rows are known (anomod_spans::parent_row): spans [lo, hi)
+// of svc_flags, dur_us and the row column as a plain stream, 10 B/span, into
+// the same table forms — no ids, no trace bounds, no scan.  A thread takes 4
+// consecutive spans per load group (16 B + 16 B + 8 B), kRowLoad groups per
+// round; the next round's loads are issued before this round's records.  The
+// up to 3 spans before the first and after the last 4-aligned position are
+// read one by one by the first workgroup (the columns are 256-B aligned, so
+// alignment is that of the span position).  S0: the service count the rows
+// were written with (rows S0 / S0 + 1 are root / orphan: this call's S / S +
+// 1); a row of all ones is no span.  kHtKeys writes the exact-quantile keys
+// (edge << 32 | dur by span position) instead of recording.
+constexpr int kRowLoad = 2;
+struct RowRegs {
+  u32x4 sf[kRowLoad], dr[kRowLoad];
+  u32x2 rw[kRowLoad];
+};
+template <int HT, int ST>
+__global__ __launch_bounds__(kThreads) void edge_row_kernel(
+    const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
+    const uint16_t* __restrict__ rows, uint64_t lo, uint64_t hi, uint32_t S, uint32_t S0,
+    uint32_t E, Table tab) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[HT == kHtKeys ? 16 : kOffWave];
+  const int tid = threadIdx.x;
+  if constexpr (HT != kHtKeys) {
+    tables_init<HT, ST>(smem, E, tid);
+    __syncthreads();
+  }
+  auto one = [&](uint64_t g, uint32_t sf, uint32_t d, uint32_t row) {
+    if (row == 0xFFFFu) return;
+    const uint32_t p = row >= S0 ? row - S0 + S : row;
+    const uint32_t edge = p * S + (sf & 0xFFFFu);
+    if constexpr (HT == kHtKeys)
+      tab.keys[g] = ((unsigned long long)edge << 32) | d;
+    else
+      record<HT, ST>(smem, edge, d, sf >> 16, tab);
+  };
+  const uint64_t up = (lo + 3ull) & ~3ull;
+  const uint64_t a0 = up < hi ? up : hi;                   // head [lo, a0)
+  const uint64_t a1 = (hi & ~3ull) > a0 ? (hi & ~3ull) : a0;  // groups [a0, a1), tail [a1, hi)
+  if (blockIdx.x == 0 && tid < 8) {
+    const uint64_t g = tid < 4 ? lo + (uint64_t)tid : a1 + (uint64_t)(tid - 4);
+    if (g < (tid < 4 ? a0 : hi)) one(g, svcfl[g], dur[g], rows[g]);
+  }
+  const uint64_t ng = (a1 - a0) / 4;
+  const u32x4* sf4 = reinterpret_cast<const u32x4*>(svcfl + a0);
+  const u32x4* dr4 = reinterpret_cast<const u32x4*>(dur + a0);
+  const u32x2* rw2 = reinterpret_cast<const u32x2*>(rows + a0);
+  // groups past the end re-read the last one (no branch around a load) and
+  // take skip rows
+  auto load = [&](uint64_t g0, RowRegs& R) {
+#pragma unroll
+    for (int j = 0; j < kRowLoad; ++j) {
+      const uint64_t gi = g0 + (uint64_t)(j * kThreads + tid);
+      const uint64_t gc = gi < ng ? gi : ng - 1;
+      R.sf[j] = sf4[gc];
+      R.dr[j] = dr4[gc];
+      const u32x2 w = rw2[gc];
+      R.rw[j] = gi < ng ? w : u32x2{0xFFFFFFFFu, 0xFFFFFFFFu};
+    }
+  };
+  constexpr uint64_t kPerBlock = (uint64_t)kThreads * kRowLoad;
+  uint64_t g0 = (uint64_t)blockIdx.x * kPerBlock;
+  RowRegs cur;
+  if (g0 < ng) load(g0, cur);
+  while (g0 < ng) {
+    const uint64_t gn = g0 + (uint64_t)gridDim.x * kPerBlock;
+    RowRegs nxt = cur;
+    if (gn < ng) load(gn, nxt);
+#pragma unroll
+    for (int j = 0; j < kRowLoad; ++j) {
+      const uint64_t g = a0 + 4ull * (g0 + (uint64_t)(j * kThreads + tid));
+      one(g, cur.sf[j].x, cur.dr[j].x, cur.rw[j].x & 0xFFFFu);
+      one(g + 1, cur.sf[j].y, cur.dr[j].y, cur.rw[j].x >> 16);
+      one(g + 2, cur.sf[j].z, cur.dr[j].z, cur.rw[j].y & 0xFFFFu);
+      one(g + 3, cur.sf[j].w, cur.dr[j].w, cur.rw[j].y >> 16);
+    }
+    cur = nxt;
+    g0 = gn;
+  }
+  if constexpr (HT != kHtKeys) {
+    __syncthreads();
+    tables_flush<HT, ST>(smem, E, tab, tid);  // (the caller sets tab.occupancy)
+  }
 }
 
 // Count + nearest-rank quantiles per edge from the merged histogram: one
@@ -1363,11 +1469,17 @@ struct Pick {
 
 // mode: kModeAuto only for the pair forms, kModeResume only for the compact
 // forms of the SN / TrainTicket widths (the instantiations that exist).
-Pick pick_kernel(uint32_t E, bool compact, bool uni, int mode = kModeNormal, bool long_set = false) {
+// rows: the instantiation that also fills the set's parent-row column (the
+// forms of known-form launches only: kModeNormal / the wide scan).
+Pick pick_kernel(uint32_t E, bool compact, bool uni, int mode = kModeNormal, bool long_set = false,
+                 bool rows = false) {
   const uint64_t keys = (uint64_t)E * kBins + 1;  // largest stored key
   const bool lds_hist = keys < (1ull << 31);  // >= 1 count bit above the key
 #define ANOMOD_PICK(H, S_, NAME)                                                               \
-  return Pick{uni ? edge_agg_kernel<H, S_, true> : edge_agg_kernel<H, S_, false>, H, S_, NAME}
+  return Pick{rows ? (uni ? edge_agg_kernel<H, S_, true, kModeNormal, true>                    \
+                          : edge_agg_kernel<H, S_, false, kModeNormal, true>)                  \
+                   : (uni ? edge_agg_kernel<H, S_, true> : edge_agg_kernel<H, S_, false>),     \
+              H, S_, NAME}
 #define ANOMOD_PICK_M(H, S_, M, NAME)                                                          \
   return Pick{uni ? edge_agg_kernel<H, S_, true, M> : edge_agg_kernel<H, S_, false, M>, H, S_, NAME}
   if (lds_hist && E <= kLdsEdges && mode == kModeResume)
@@ -1379,8 +1491,9 @@ Pick pick_kernel(uint32_t E, bool compact, bool uni, int mode = kModeNormal, boo
   if (lds_hist && E > kLdsEdges && E <= kWideEdges && !compact && mode == kModeAuto)
     ANOMOD_PICK_M(kHtPair, kStWide, kModeAuto, "edge_agg_kernel<lds_hist,wide_stats,auto>");
   if (lds_hist && E <= kLdsEdges && compact && uni && long_set && mode == kModeNormal)
-    return Pick{edge_agg_kernel<kHtCompact, kStDirect, true, kModeWideScan>, kHtCompact, kStDirect,
-                "edge_agg_kernel<lds_compact_hist,lds_stats,wide_scan>"};
+    return Pick{rows ? edge_agg_kernel<kHtCompact, kStDirect, true, kModeWideScan, true>
+                     : edge_agg_kernel<kHtCompact, kStDirect, true, kModeWideScan>,
+                kHtCompact, kStDirect, "edge_agg_kernel<lds_compact_hist,lds_stats,wide_scan>"};
   if (lds_hist && E <= kLdsEdges && compact)  // a set that overflowed the pair table
     ANOMOD_PICK(kHtCompact, kStDirect, "edge_agg_kernel<lds_compact_hist,lds_stats>");
   if (lds_hist && E <= kLdsEdges) ANOMOD_PICK(kHtPair, kStDirect, "edge_agg_kernel<lds_hist,lds_stats>");
@@ -1395,6 +1508,70 @@ Pick pick_kernel(uint32_t E, bool compact, bool uni, int mode = kModeNormal, boo
   ANOMOD_PICK(kHtHbm, kStHbm, "edge_agg_kernel<hbm_hist,hbm_stats>");
 #undef ANOMOD_PICK
 #undef ANOMOD_PICK_M
+}
+
+// ---- parent rows of a resident set ------------------------------------------
+// Whether a call may fill / read the set's parent-row column: a grouped set
+// that outlives the call, with none of the experiment overrides set
+// (ANOMOD_HIST_FORM and ANOMOD_UNIQUE_SCAN ask for a walk kernel by name;
+// ANOMOD_PARENT_ROWS=0 is the A/B switch).  Otherwise the call walks the
+// traces as if the column did not exist.
+bool rows_allowed(const anomod_spans* s) {
+  const char* f = getenv("ANOMOD_PARENT_ROWS");
+  if (f && !strcmp(f, "0")) return false;
+  if (getenv("ANOMOD_HIST_FORM") || getenv("ANOMOD_UNIQUE_SCAN")) return false;
+  return s->keep_rows && s->grouped;
+}
+
+bool rows_ready(const anomod_spans* s) {
+  return rows_allowed(s) && s->parent_row && s->rows_done;
+}
+
+using RowFn = void (*)(const uint32_t*, const uint32_t*, const uint16_t*, uint64_t, uint64_t,
+                       uint32_t, uint32_t, uint32_t, Table);
+struct RowPick {
+  RowFn fn;
+  int ht;
+  const char* name;
+};
+
+// The stream kernel of the table form pick_kernel gives the set.
+RowPick pick_row_kernel(uint32_t E, bool compact) {
+  const Pick pk = pick_kernel(E, compact, false);
+  if (pk.ht == kHtPair && pk.st == kStDirect)
+    return {edge_row_kernel<kHtPair, kStDirect>, kHtPair, "edge_row_kernel<lds_hist,lds_stats>"};
+  if (pk.ht == kHtCompact && pk.st == kStDirect)
+    return {edge_row_kernel<kHtCompact, kStDirect>, kHtCompact,
+            "edge_row_kernel<lds_compact_hist,lds_stats>"};
+  if (pk.ht == kHtPair && pk.st == kStWide)
+    return {edge_row_kernel<kHtPair, kStWide>, kHtPair, "edge_row_kernel<lds_hist,wide_stats>"};
+  if (pk.ht == kHtCompact && pk.st == kStWide)
+    return {edge_row_kernel<kHtCompact, kStWide>, kHtCompact,
+            "edge_row_kernel<lds_compact_hist,wide_stats>"};
+  if (pk.ht == kHtCompact && pk.st == kStSlot)
+    return {edge_row_kernel<kHtCompact, kStSlot>, kHtCompact,
+            "edge_row_kernel<lds_compact_hist,slot_stats>"};
+  return {edge_row_kernel<kHtHbm, kStHbm>, kHtHbm, "edge_row_kernel<hbm_hist,hbm_stats>"};
+}
+
+// The set's spans [rows_lo, rows_hi) through fn, at most max_launch_spans()
+// per launch (the LDS tables' u32 counters).
+int launch_rows(anomod_ctx* ctx, const anomod_spans* s, RowFn fn, uint32_t S, uint32_t E,
+                const Table& tab) {
+  int per_cu = 0;
+  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                      &per_cu, reinterpret_cast<const void*>(fn), kThreads, 0));
+  const uint64_t cap = max_launch_spans();
+  constexpr uint64_t kRound = (uint64_t)kThreads * kRowLoad * 4;  // spans per workgroup round
+  for (uint64_t a = s->rows_lo; a < s->rows_hi; a += cap) {
+    const uint64_t b = std::min<uint64_t>(s->rows_hi, a + cap);
+    const uint64_t want = (b - a + kRound - 1) / kRound;
+    const uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * (per_cu > 0 ? per_cu : 1), want);
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->svc_flags,
+                       s->dur_us, s->parent_row, a, b, S, s->rows_S, E, tab);
+    ANOMOD_HIP(ctx, hipGetLastError());
+  }
+  return ANOMOD_OK;
 }
 
 // Device table layout inside ctx->d_table: hist | err | sum (u64, one sum
@@ -1637,11 +1814,17 @@ int span_scan_choice(anomod_ctx* ctx, const anomod_spans* s, unsigned long long*
 size_t span_edge_keys_ws_bytes(const anomod_spans* s) { return 256 + big_capacity(s) * 8; }
 
 int span_edge_keys(anomod_ctx* ctx, const anomod_spans* spans, uint32_t S,
-                   unsigned long long* keys, unsigned long long* ws) {
+                   unsigned long long* keys, unsigned long long* ws, bool use_rows) {
   if (!spans->n_spans || !spans->n_traces) return ANOMOD_OK;
   const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
   Table tab{};
   tab.keys = keys;
+  // a set with its parent rows: the keys from the row stream, no walk
+  if (use_rows && rows_ready(spans)) {
+    if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
+      fprintf(stderr, "anomod: edge key kernel edge_row_kernel<keys>\n");
+    return launch_rows(ctx, spans, edge_row_kernel<kHtKeys, kStHbm>, S, E, tab);
+  }
   tab.ctr = ws;
   tab.big = ws + 1;
   tab.big_list = ws + 32;
@@ -1723,14 +1906,40 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
     form = 1;
     spans->hist_form = 1;
   }
-  const bool probe = form < 0 && pair_ok && !autof && spans->n_traces > 0;
+  if (local == ANOMOD_OK) local = bind(ctx);
+  // Parent rows.  The first-match parent of a span depends only on the set's
+  // id columns and trace_ptr, which a resident set never changes: the first
+  // aggregation of a set that outlives the call (`build`) walks the traces
+  // once, in the ROWS instantiation that also stores every span's parent row
+  // into the set's column (the long-trace pass writes its rows there too),
+  // and every later one (`stream`) reads svc_flags, dur_us and the rows, 10
+  // instead of 24 B/span (edge_row_kernel).  The walk is then never run again
+  // for the set, so a form-unknown set is not probed: it runs whole in the
+  // compact form with the occupancy report and learns its form from that
+  // (`learn`), as sets of <= 4 x 2^19 spans always did.  When the column
+  // cannot be allocated the call runs as before and the set stays without.
+  const bool rows_ok = local == ANOMOD_OK && rows_allowed(spans) && spans->n_traces > 0;
+  const bool stream = rows_ok && spans->parent_row && spans->rows_done;
+  bool build = rows_ok && !stream;
+  if (build && !spans->parent_row) {
+    void* p = nullptr;
+    if (dev_malloc(ctx, &p, spans->n_spans * 2) == hipSuccess) {
+      spans->parent_row = static_cast<uint16_t*>(p);
+    } else {
+      (void)hipGetLastError();
+      build = false;
+    }
+  }
+  const bool learn = (build || stream) && form < 0 && pair_ok;
+  const bool probe = form < 0 && pair_ok && !autof && spans->n_traces > 0 && !learn;
   // the probe's compact form (the forward scan when the order is still unknown)
   const Pick pc = pick_kernel(E, true, uni, kModeNormal, long_set);
-  Pick pk = pick_kernel(E, form == 1, uni, autof ? kModeAuto : kModeNormal, long_set);
+  Pick pk = pick_kernel(E, form == 1 || learn, uni, autof ? kModeAuto : kModeNormal, long_set,
+                        build);
   const Pick pr = autof ? pick_kernel(E, true, uni, kModeResume) : pk;  // the resume launch's form
+  const RowPick rp = pick_row_kernel(E, form == 1 || learn);
   // As many workgroups as are resident at once (LDS / registers decide).
   int per_cu = 0, per_cu_r = 0;
-  if (local == ANOMOD_OK) local = bind(ctx);
   if (local == ANOMOD_OK &&
       (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(pk.fn),
                                                     kThreads, 0) != hipSuccess ||
@@ -1741,16 +1950,22 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   }
   const uint64_t grid = (uint64_t)ctx->num_cus * (uint64_t)(per_cu > 0 ? per_cu : 1);
   const uint64_t grid_r = (uint64_t)ctx->num_cus * (uint64_t)(per_cu_r > 0 ? per_cu_r : 1);
-  const Layout L(E, big_cap, spans->n_spans, autof ? grid * kWavesPerWG : 0);
+  // (the long-trace pass writes its rows into the set's column when that is
+  // being filled, and a stream call lists nothing)
+  const Layout L(E, stream ? 0 : big_cap, build ? 0 : spans->n_spans,
+                 autof ? grid * kWavesPerWG : 0);
+  // (+ 16: the span range of a filled column)
+  const size_t small = (L.end_small - L.off_err + 7) & ~size_t(7);
   if (local == ANOMOD_OK) local = ensure_table(ctx, L.bytes);
-  if (local == ANOMOD_OK) local = ensure_host_stage(ctx, L.end_small - L.off_err);
+  if (local == ANOMOD_OK) local = ensure_host_stage(ctx, small + 16);
   if (int rc = comm_agree(ctx, local)) return rc;
-  const Table tab = table_at(ctx, L, E);
+  Table tab = table_at(ctx, L, E);
+  if (build) tab.bpar = spans->parent_row;
   if (int rc = table_clear(ctx, L, tab, E)) return rc;
 
   // A first aggregation's probes (order, histogram form) run back to back
   // and are read back with one host wait.
-  const bool oprobe = spans->n_traces > 0 && need_order_probe(spans);
+  const bool oprobe = spans->n_traces > 0 && need_order_probe(spans) && !stream;
   auto* hst = static_cast<unsigned long long*>(ctx->h_stage);  // [0..1] order, [2] occupancy
   if (oprobe)  // scratch: the big counters' 4th and 5th words
     if (int rc = probe_order_launch(ctx, spans, tab.big + 3, hst)) return rc;
@@ -1758,10 +1973,23 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
     ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     probe_order_take(spans, hst);
     uni = use_unique(spans);
-    pk = pick_kernel(E, form == 1, uni, autof ? kModeAuto : kModeNormal, long_set);
+    pk = pick_kernel(E, form == 1 || learn, uni, autof ? kModeAuto : kModeNormal, long_set, build);
+  }
+  auto* h_range = reinterpret_cast<uint64_t*>(static_cast<char*>(ctx->h_stage) + small);
+  if (build) {  // the spans the traces cover: what the later calls stream
+    ANOMOD_HIP(ctx, hipMemcpyAsync(h_range, spans->trace_ptr, 8, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+    ANOMOD_HIP(ctx, hipMemcpyAsync(h_range + 1, spans->trace_ptr + spans->n_traces, 8,
+                                   hipMemcpyDeviceToHost, ctx->stream));
   }
   if (int rc = stage_begin(ctx, kStageEdgeAgg)) return rc;
-  if (spans->n_traces > 0) {
+  if (stream) {
+    if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
+      fprintf(stderr, "anomod: edge aggregation kernel %s\n", rp.name);
+    Table tr = tab;
+    tr.occupancy = learn;
+    if (int rc = launch_rows(ctx, spans, rp.fn, S, E, tr)) return rc;
+  } else if (spans->n_traces > 0) {
     // A workgroup's LDS counters (histogram slots, errors) are u32 and the
     // dynamic tail may hand one workgroup any share of a launch, so a launch
     // covers < 2^32 spans: larger sets run as several launches over whole
@@ -1801,7 +2029,8 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
       cuts[0] = P;
     }
     if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
-      fprintf(stderr, "anomod: edge aggregation kernel %s\n", pk.name);
+      fprintf(stderr, "anomod: edge aggregation kernel %s%s\n", pk.name,
+              build ? " + parent rows" : "");
     for (size_t k = 0; k + 1 < cuts.size(); ++k) {
       if (cuts[k] >= cuts[k + 1]) continue;
       if (k > 0) {
@@ -1811,6 +2040,7 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
       Table tk = tab;
       tk.t_base = cuts[k];
       tk.mode = autof ? kModeAuto : kModeNormal;
+      tk.occupancy = learn;
       hipLaunchKernelGGL(pk.fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream,
                          spans->span_id, spans->parent_span_id, spans->svc_flags, spans->dur_us,
                          spans->trace_ptr + cuts[k], cuts[k + 1] - cuts[k], S, E, tk);
@@ -1823,17 +2053,31 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
         ANOMOD_HIP(ctx, hipGetLastError());
       }
     }
-    if (big_cap) ANOMOD_HIP(ctx, launch_big_for(ctx, spans, S, E, tab));
+    if (big_cap) {
+      Table tb = tab;
+      tb.occupancy = learn;
+      ANOMOD_HIP(ctx, launch_big_for(ctx, spans, S, E, tb));
+    }
   }
   if (int rc = stage_end(ctx, kStageEdgeAgg)) return rc;
   unsigned long long ovf[2] = {0ull, 0ull};
   if (int rc = table_finish(ctx, L, tab, E, out, ovf)) return rc;
+  if (build) {  // every launch ran: the column is complete
+    spans->rows_S = S;
+    spans->rows_lo = h_range[0];
+    spans->rows_hi = h_range[1];
+    spans->rows_done = true;
+  }
+  // a compact-form run that reported its fullest workgroup's slots: at most
+  // half the pair table's says pair
+  if (learn) spans->hist_form = ovf[1] <= kPairSlots / 2 ? 0 : 1;
+  const int ran_ht = stream ? rp.ht : pk.ht;
   // The set's form from here on: compact when a workgroup of a first
   // aggregation stopped at a saturated pair table, or when more than 1/64 of
   // the spans were counted in HBM past a full one (the set touches more (edge,
   // bin) keys than 8 Ki slots hold, e.g. random call trees over every service
   // pair); else pair.  Same results either way.
-  if (pk.ht == kHtPair) {
+  if (ran_ht == kHtPair) {
     if (ovf[1] > 0 || ovf[0] * 64ull > spans->n_spans) spans->hist_form = 1;
     else if (spans->hist_form < 0) spans->hist_form = 0;
   }
@@ -1887,7 +2131,7 @@ int anomod_edge_quantiles_exact(anomod_ctx* ctx, const anomod_spans* spans, uint
   if (e == hipSuccess && n && spans->n_traces) {
     // per-span (edge, latency) keys from the aggregation kernel's own walk and
     // parent rule, then one radix sort over edge|dur
-    rc = span_edge_keys(ctx, spans, S, keys, d_ctr);
+    rc = span_edge_keys(ctx, spans, S, keys, d_ctr, true);
     int passes = 0;
     if (rc == ANOMOD_OK)
       e = radix_sort_u64(reinterpret_cast<const uint64_t*>(keys),
@@ -1920,9 +2164,32 @@ int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t 
   ANOMOD_REQUIRE(nullptr, ctx && soa && out, "anomod_edge_aggregate: NULL argument");
   anomod_spans* s = nullptr;
   if (int rc = anomod_spans_upload(ctx, soa, n_spans, trace_ptr, n_traces, &s)) return rc;
+  s->keep_rows = false;  // freed below: parent rows would never be read again
   const int rc = anomod_edge_aggregate_spans(ctx, s, out->n_services, out);
   anomod_spans_free(s);
   return rc;
+}
+
+int anomod_spans_parent_rows(anomod_ctx* ctx, const anomod_spans* spans, uint16_t* out_host,
+                             uint32_t S) {
+  ANOMOD_REQUIRE(nullptr, ctx && spans, "anomod_spans_parent_rows: NULL argument");
+  ANOMOD_REQUIRE(ctx, out_host || spans->n_spans == 0, "anomod_spans_parent_rows: NULL destination");
+  ANOMOD_REQUIRE(ctx, S >= 1 && S <= 4096, "n_services=%u out of range [1, 4096]", S);
+  ANOMOD_REQUIRE(ctx, spans->device == ctx->device, "span set lives on another device");
+  if (!spans->parent_row || !spans->rows_done) {
+    set_error(ctx, "span set holds no parent rows (no grouped aggregation filled them yet)");
+    return ANOMOD_ESTATE;
+  }
+  ANOMOD_REQUIRE(ctx, spans->max_svc < S, "span service index %u >= n_services %u",
+                 spans->max_svc, S);
+  if (int rc = bind(ctx)) return rc;
+  ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint64_t i = 0; i < spans->n_spans; ++i) out_host[i] = 0xFFFFu;
+  const uint64_t lo = spans->rows_lo, n = spans->rows_hi - lo;
+  if (n) ANOMOD_HIP(ctx, hipMemcpy(out_host + lo, spans->parent_row + lo, n * 2, hipMemcpyDeviceToHost));
+  for (uint64_t i = lo; i < lo + n; ++i)
+    if (out_host[i] >= spans->rows_S) out_host[i] = (uint16_t)(out_host[i] - spans->rows_S + S);
+  return ANOMOD_OK;
 }
 
 }  // extern "C"

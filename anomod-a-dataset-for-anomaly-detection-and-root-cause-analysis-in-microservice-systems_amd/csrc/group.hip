@@ -850,6 +850,9 @@ anomod_spans view_of(const anomod_spans* in, const GroupResult& g) {
   v.svc_flags = g.cols.sf;
   v.dur_us = g.cols.dur;
   v.trace_ptr = g.tptr;
+  // a view over the ctx's grouping workspace, gone after the call: it must
+  // not be given a parent-row column (nobody would free or read it)
+  v.keep_rows = false;
   return v;
 }
 

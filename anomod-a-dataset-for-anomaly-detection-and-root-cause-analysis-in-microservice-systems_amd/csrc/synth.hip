@@ -396,7 +396,7 @@ void free_spans(anomod_spans* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
   void* ptrs[] = {s->trace_hash, s->span_id, s->parent_span_id, s->svc_flags, s->dur_us,
-                  s->trace_ptr, s->start_us};
+                  s->trace_ptr, s->start_us, s->parent_row};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete s;
@@ -767,6 +767,7 @@ int anomod_edge_aggregate_host(anomod_ctx* ctx, const anomod_span_soa* soa, uint
     s->order = (int8_t)*scan_order;
     s->hist_form = (int8_t)*hist_form;
     s->max_trace_len = max_len;
+    s->keep_rows = false;  // refilled per call: parent rows would never be read again
     local = fill_set(ctx, s, soa, n_spans, trace_ptr, n_traces, false);
   }
   if (local != ANOMOD_OK) return comm_agree(ctx, local);  // peers learn of it before their reduce

@@ -172,6 +172,20 @@ int anomod_spans_hist_compact(const anomod_spans* spans, int* compact);
  * uploaded set (each in [-1, 1]); results never depend on them.           */
 int anomod_spans_hints(const anomod_spans* spans, int* scan_order, int* hist_form);
 int anomod_spans_set_hints(anomod_spans* spans, int scan_order, int hist_form);
+/* Diagnostic: the parent rows a resident grouped set keeps once its first
+ * anomod_edge_aggregate_spans has run — per span position, the service index
+ * of the span's first-match parent inside its trace, n_services for a root
+ * span (parent reference 0), n_services + 1 for an orphan (reference not in
+ * the trace) — copied to out_host[n_spans]; positions outside every trace
+ * read 0xFFFF.  Later aggregations and anomod_edge_quantiles_exact of the
+ * set read this column (2 B/span of HBM, allocated by that first call; a
+ * failed allocation only leaves the set without it) instead of resolving the
+ * parents again; unique ids, hints and start times do not affect it.
+ * ANOMOD_ESTATE when the set holds none: no aggregation yet, a call run with
+ * ANOMOD_PARENT_ROWS=0 / ANOMOD_HIST_FORM / ANOMOD_UNIQUE_SCAN set, an
+ * ungrouped set, or the column could not be allocated.                      */
+int anomod_spans_parent_rows(anomod_ctx* ctx, const anomod_spans* spans, uint16_t* out_host,
+                             uint32_t n_services);
 /* Copy a host span set to HBM.  Replaces the in-memory hand-off between
  * json.load and the per-span loop of jaeger_to_csv.py:12-32 /
  * trace_collector.py:519-531.                                              */
