@@ -18,11 +18,11 @@ from .decode import (MetricMatrix, decode_jaeger, decode_native, load_trace_file
 from .device import (Context, DeviceGraph, DeviceSeries, DeviceSpans, SynthSpec, device_count,
                      device_count_safe, synth_generate_host, synth_graph_csr, synth_services)
 from .engine import (Experiment, Features, default_context, fault_target, features, hit_at,
-                     load_experiment, rank, trace_window_scores)
+                     load_experiment, load_window_scores, rank, trace_window_scores)
 from . import api
 from .segments import SegmentSet, service_name_of, trace_infos
 from .writers import jaeger_to_csv, write_jaeger_csv, write_metric_long_csv
-from .spans import (CriticalPath, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
+from .spans import (CriticalPath, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
                     TraceSpectrum, TraceStructure, edge_rows, spectrum_thresholds)
 
 __all__ = [
@@ -37,7 +37,7 @@ __all__ = [
     "SegmentSet", "service_name_of", "trace_infos", "analyze_trace_patterns",
     "jaeger_to_csv", "write_jaeger_csv", "write_metric_long_csv", "decode_native",
     "load_trace_file", "api", "trace_window_scores", "TraceSpectrum", "spectrum_thresholds",
-    "CriticalPath", "TraceShapes", "ErrorOrigins",
+    "CriticalPath", "TraceShapes", "ErrorOrigins", "EdgeLoad", "load_window_scores",
 ]
 
 

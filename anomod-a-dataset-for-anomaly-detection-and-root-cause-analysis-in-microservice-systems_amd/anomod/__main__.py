@@ -1,6 +1,7 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
                                  [--spectrum] [--critical-path] [--shapes]
-                                 [--error-origins] [--baseline <trace file|dir>]
+                                 [--error-origins] [--trace-step S [--trace-load]]
+                                 [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
 Computes the RCA features of one experiment on the GPU and writes them as JSON:
@@ -54,6 +55,22 @@ def error_origins_doc(eo) -> dict:
                          for i, s in enumerate(eo.services)}}
 
 
+def edge_load_doc(load) -> dict:
+    """The "edge_load" object of the features JSON: the window range, the
+    spans that touch no window and, per active edge, the busy time and the
+    carried calls of every window."""
+    S = len(load.services)
+    rows = []
+    for r in load.active_rows().tolist():
+        p, c = divmod(r, S)
+        rows.append({"parent": "ROOT" if p == S else "ORPHAN" if p == S + 1 else load.services[p],
+                     "child": load.services[c],
+                     "busy_us": [int(v) for v in load.busy_us[:, r]],
+                     "carried": [int(v) for v in load.carried[:, r]]})
+    return {"t0_us": int(load.t0_us), "step_us": int(load.step_us),
+            "windows": int(load.n_windows), "outside": int(load.outside), "edges": rows}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m anomod")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -68,6 +85,10 @@ def main(argv=None) -> int:
     f.add_argument("--trace-quantile", type=int, metavar="PCT",
                    help="with --trace-step: also score each edge's exact per-window latency "
                         "quantile of this percentage (0..99, e.g. 99)")
+    f.add_argument("--trace-load", action="store_true",
+                   help="with --trace-step: also score each edge's per-window busy time (how "
+                        "long its calls were open inside every window, so calls that pile up "
+                        "show in every window they last through) and write it as \"edge_load\"")
     f.add_argument("--self-time", action="store_true",
                    help="also compute the self-time (exclusive latency) edge table and "
                         "write it as \"self_edges\"")
@@ -99,6 +120,8 @@ def main(argv=None) -> int:
         from .writers import jaeger_to_csv
         return jaeger_to_csv(args.input, args.output)
 
+    if args.trace_load and args.trace_step is None:
+        ap.error("--trace-load needs --trace-step")
     exp = load_experiment(args.traces, metrics=args.metrics)
     baseline = None
     if args.baseline:
@@ -108,7 +131,8 @@ def main(argv=None) -> int:
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
                      critical_path=args.critical_path, trace_quantile=args.trace_quantile,
-                     shapes=args.shapes, error_origins=args.error_origins)
+                     shapes=args.shapes, error_origins=args.error_origins,
+                     trace_load=args.trace_load)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -145,6 +169,10 @@ def main(argv=None) -> int:
     if feats.error_origins is not None:
         doc["error_origins"] = error_origins_doc(feats.error_origins)
         doc["loop_spans"] = int(feats.error_origins.loop_spans)
+    if feats.edge_load is not None:
+        doc["edge_load"] = edge_load_doc(feats.edge_load)
+        doc["load_scores"] = dict(zip(feats.edges.services,
+                                      map(float, feats.params["components"]["load"])))
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

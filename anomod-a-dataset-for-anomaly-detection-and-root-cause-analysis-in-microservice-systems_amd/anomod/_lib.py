@@ -29,7 +29,8 @@ _STATUS = {EINVAL: "EINVAL", EHIP: "EHIP", ERCCL: "ERCCL", ENOMEM: "ENOMEM", EST
 
 (STAGE_EDGE_AGG, STAGE_EDGE_FINAL, STAGE_EDGE_REDUCE, STAGE_EWMA, STAGE_PAGERANK,
  STAGE_TRACE_STRUCT, STAGE_SEGMENTS, STAGE_SUMMARY, STAGE_GROUP,
- STAGE_EDGE_WINDOWS, STAGE_EDGE_WINDOW_KERNEL) = range(11)
+ STAGE_EDGE_WINDOWS, STAGE_EDGE_WINDOW_KERNEL, STAGE_EDGE_LOAD, STAGE_EDGE_LOAD_KERNEL,
+ STAGE_EDGE_LOAD_SCAN) = range(14)
 (HOST_GROUP_ALLOC, HOST_GROUP_PINNED, HOST_GROUP_WALL, HOST_UPLOAD_SETUP,
  HOST_SET_ALLOC) = range(5)
 HOST_SLOTS = 5
@@ -82,6 +83,18 @@ class EdgeWindowsC(C.Structure):
         ("errors", C.POINTER(C.c_uint64)),
         ("sum_us", C.POINTER(C.c_uint64)),
         ("max_us", C.POINTER(C.c_uint32)),
+        ("outside", C.c_uint64),
+    ]
+
+
+class EdgeLoadC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("t0_us", C.c_uint64),
+        ("step_us", C.c_uint64),
+        ("busy_us", C.POINTER(C.c_uint64)),
+        ("carried", C.POINTER(C.c_uint64)),
         ("outside", C.c_uint64),
     ]
 
@@ -239,6 +252,8 @@ _SIGS = {
     "anomod_spans_get_start_us": (_i32, [_vp, _vp, _P(_u64)]),
     "anomod_spans_fill_start_synthetic": (_i32, [_vp, _vp, _u64, _u64, _u64]),
     "anomod_edge_windows_spans": (_i32, [_vp, _vp, _P(EdgeWindowsC)]),
+    "anomod_edge_load_spans": (_i32, [_vp, _vp, _P(EdgeLoadC)]),
+    "anomod_edge_load_scan_segment": (C.c_uint32, []),
     "anomod_edge_window_quantiles_spans": (_i32, [_vp, _vp, _P(EdgeWindowQuantilesC)]),
     "anomod_decoded_start_us": (_i32, [_vp, _P(_u64)]),
     "anomod_spans_set_unique_ids": (_i32, [_vp, C.c_int]),

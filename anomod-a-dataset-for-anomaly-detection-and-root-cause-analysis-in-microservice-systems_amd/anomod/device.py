@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import (CriticalPath, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
+from .spans import (CriticalPath, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
                     TraceSpectrum, TraceStructure, edge_rows)
 
 
@@ -433,6 +433,39 @@ class Context:
                                                             C.byref(cs)))
             win.outside = int(cs.outside)
             return win
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def edge_load(self, spans: DeviceSpans | SpanSet, t0_us: int, step_us: int,
+                  n_windows: int, outputs=("busy_us", "carried")) -> EdgeLoad:
+        """Per-window edge load of a grouped set with start times
+        (anomod_edge_load_spans): the windows and rows of edge_windows;
+        .busy_us[w, row] the time the edge's calls were open inside window w,
+        .carried[w, row] the calls still open when it opens; spans that touch
+        no window are counted in .outside.  A call that starts before t0_us
+        and reaches into the range is clipped, not dropped.  Rank-local.
+        `outputs` names the tables to compute (the others stay zero).  A
+        resident set that has been aggregated is read as one stream (its
+        parent rows); a host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            if spans.start_us is None:
+                raise ValueError("span set has no start_us column")
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            if not 1 <= int(n_windows) <= 65536 or int(n_windows) * edge_rows(S) > 1 << 24:
+                raise L.AnomodError(L.EINVAL, f"n_windows={n_windows} outside [1, 65536] or "
+                                    f"n_windows * edge rows > 2^24 (n_services={S})")
+            load = EdgeLoad.empty(spans.services, t0_us, step_us, n_windows)
+            cs = L.EdgeLoadC(
+                S, n_windows, t0_us, step_us,
+                L.ptr(load.busy_us if "busy_us" in outputs else None, C.c_uint64),
+                L.ptr(load.carried if "carried" in outputs else None, C.c_uint64), 0)
+            self._check(self._lib.anomod_edge_load_spans(self.handle, spans.handle, C.byref(cs)))
+            load.outside = int(cs.outside)
+            return load
         finally:
             if tmp is not None:
                 tmp.free()

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import (EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes, TraceSpectrum,
+from .spans import (EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes, TraceSpectrum,
                     edge_rows, spectrum_thresholds)
 
 # --------------------------------------------------------------------------
@@ -176,6 +176,8 @@ class Features:
     shapes: TraceShapes | None = None
     # features(error_origins=True): where failures started and how far they travelled
     error_origins: ErrorOrigins | None = None
+    # features(trace_load=True): per-window busy time and carried calls of every edge
+    edge_load: EdgeLoad | None = None
 
 
 _default_ctx: Context | None = None
@@ -256,13 +258,29 @@ def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int,
     return out
 
 
+def load_window_scores(Z: np.ndarray, load: EdgeLoad, S: int) -> np.ndarray:
+    """Per-service load score from the window scores Z [n, active edges] of
+    load.matrix(), by the rule of trace_window_scores: the first score window
+    is dropped, a column scores the mean of its top k = max(1, n_left // 20)
+    windows, and a service takes the max over the edges it is the child of."""
+    out = np.zeros(S)
+    Z = np.asarray(Z, np.float64)[1:]
+    if Z.shape[0] == 0 or Z.shape[1] == 0:
+        return out
+    k = max(1, Z.shape[0] // 20)
+    top = np.sort(Z, axis=0)[-k:].mean(axis=0)
+    child = load.active_rows() % S
+    np.maximum.at(out, child, top[: child.shape[0]])
+    return out
+
+
 MAX_TRACE_WINDOWS = 65536          # anomod_edge_windows: T <= 65536, T * E <= 2^24
 MAX_TRACE_CELLS = 1 << 24
 
 
-def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float,
-                   min_count: int, quantile: int | None = None
-                   ) -> tuple[EdgeWindows, np.ndarray]:
+def _trace_range(spans: SpanSet, step_s: float) -> tuple[int, int, int]:
+    """(t0_us, step_us, n_windows) of the window range the trace series use:
+    from the step-aligned smallest non-zero start to the largest."""
     if spans.start_us is None:
         raise ValueError("features(trace_step_s=...): the span set has no start_us column")
     step_us = max(1, int(round(step_s * 1e6)))
@@ -271,6 +289,28 @@ def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: flo
     t0 = int(nz.min()) // step_us * step_us if nz.size else 0
     T = (int(nz.max()) - t0) // step_us + 1 if nz.size else 1
     T = max(1, min(T, MAX_TRACE_WINDOWS, MAX_TRACE_CELLS // max(1, edge_rows(S))))
+    return t0, step_us, T
+
+
+def _trace_load(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float
+                ) -> tuple[EdgeLoad, np.ndarray]:
+    """The edge-load table over the range of _trace_windows (the two tables
+    line up) and its per-service score."""
+    t0, step_us, T = _trace_range(spans, step_s)
+    S = spans.n_services
+    load = ctx.edge_load(spans, t0, step_us, T)
+    mm = load.matrix().pad_to_multiple(W)
+    if mm.S == 0 or mm.T == 0:
+        return load, np.zeros(S)
+    Z = ctx.ewma_z(mm.X, 2.0 / (W + 1), W, eps)
+    return load, load_window_scores(Z, load, S)
+
+
+def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float,
+                   min_count: int, quantile: int | None = None
+                   ) -> tuple[EdgeWindows, np.ndarray]:
+    t0, step_us, T = _trace_range(spans, step_s)
+    S = spans.n_services
     if quantile is None:
         win = ctx.edge_windows(spans, t0, step_us, T)
         mm = win.matrix(min_count).pad_to_multiple(W)
@@ -290,7 +330,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              self_time: bool = False, spectrum: bool = False,
              spectrum_rows: str = "root", critical_path: bool = False,
              trace_quantile: int | None = None, shapes: bool = False,
-             error_origins: bool = False) -> Features:
+             error_origins: bool = False, trace_load: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -325,7 +365,16 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     the failures that started in a service over the spans it served — instead
     of the inclusive error rate, which also fires for every caller that merely
     relayed a callee's failure: components["error_rate"] then holds the origin
-    rate and components["error_kind"] is "origin".  No baseline is involved."""
+    rate and components["error_kind"] is "origin".  No baseline is involved.
+    With trace_load (needs trace_step_s) the spans also go through the edge
+    load table (Context.edge_load, over the same window range as the trace
+    series) -> EWMA/z at trace_W / trace_eps -> load_window_scores, and the
+    score gains 0.25 * ls / (1 + ls) (components["load"]): calls that stay
+    open pile up busy time in every window they last through, which the
+    start-window series above cannot see — a hung call is one cell of their
+    latency sum, and none at all on an edge below trace_min_count."""
+    if trace_load and trace_step_s is None:
+        raise ValueError("features(trace_load=True) needs trace_step_s")
     if trace_quantile is not None and trace_step_s is None:
         raise ValueError("features(trace_quantile=...) needs trace_step_s")
     if trace_quantile is not None and not 0 <= int(trace_quantile) <= 99:
@@ -415,9 +464,18 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
                   trace_min_count=trace_min_count)
     if trace_quantile is not None:
         params["trace_quantile"] = int(trace_quantile)
-    return Features(exp.name, edges, Z, series, score + 0.25 * tsq, params,
+    score = score + 0.25 * tsq
+    load = None
+    if trace_load:
+        load, ls = _trace_load(exp.spans, ctx, trace_step_s, trace_W, trace_eps)
+        lsq = ls / (1.0 + ls)
+        params["components"]["load"] = lsq
+        params["trace_load"] = True
+        score = score + 0.25 * lsq
+    return Features(exp.name, edges, Z, series, score, params,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
-                    spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins)
+                    spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
+                    edge_load=load)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

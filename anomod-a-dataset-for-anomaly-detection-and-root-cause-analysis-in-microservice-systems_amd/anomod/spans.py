@@ -326,6 +326,58 @@ class EdgeWindows:
 
 
 @dataclass
+class EdgeLoad:
+    """Per-window edge load of a span set with start times
+    (anomod_edge_load_spans): for window w = [t0_us + w * step_us, t0_us +
+    (w + 1) * step_us) and an edge row, busy_us is the time the edge's calls
+    were open inside the window (busy_us / step_us = the mean number in
+    flight) and carried the calls still open when the window opens.  A call is
+    followed for as long as it lasts, where EdgeWindows books it in the window
+    it starts in only.  Rows as in EdgeTable."""
+
+    services: list[str]
+    t0_us: int
+    step_us: int
+    busy_us: np.ndarray   # u64 [T, E]
+    carried: np.ndarray   # u64 [T, E]
+    outside: int = 0      # spans in traces that touch no window: dur 0, or wholly before / after
+
+    @property
+    def n_windows(self) -> int:
+        return int(self.busy_us.shape[0])
+
+    @staticmethod
+    def empty(services: list[str], t0_us: int, step_us: int, n_windows: int) -> "EdgeLoad":
+        shape = (n_windows, edge_rows(len(services)))
+        return EdgeLoad(list(services), int(t0_us), int(step_us), np.zeros(shape, np.uint64),
+                        np.zeros(shape, np.uint64))
+
+    def active_rows(self) -> np.ndarray:
+        """The edge rows with a non-zero busy or carried total, ascending."""
+        return np.nonzero((self.busy_us != 0).any(axis=0) | (self.carried != 0).any(axis=0))[0]
+
+    def matrix(self):
+        """The table as a time-major series matrix for the EWMA/z kernels: one
+        f32 column per active edge (active_rows), log2(1 + busy_us) computed
+        in f64.  No NaNs: an idle window is a 0, which is information here.
+        Series keys: ("edge_busy_us", (("parent", name), ("child", name)));
+        timestamps are the window starts in epoch seconds."""
+        from .decode import MetricMatrix
+
+        S = len(self.services)
+        T = self.n_windows
+        active = self.active_rows()
+        X = np.log2(1.0 + self.busy_us[:, active].astype(np.float64)).astype(np.float32)
+        series = []
+        for r in active.tolist():
+            p, c = divmod(r, S)
+            name = "ROOT" if p == S else "ORPHAN" if p == S + 1 else self.services[p]
+            series.append(("edge_busy_us", (("parent", name), ("child", self.services[c]))))
+        ts = (self.t0_us + np.arange(T, dtype=np.float64) * self.step_us) / 1e6
+        return MetricMatrix(X, ts, series)
+
+
+@dataclass
 class CriticalPath:
     """Critical path of a span set with start times
     (anomod_edge_critical_path_spans): the edge table of the on-path spans

@@ -34,7 +34,8 @@ struct UpItem {
 enum Stage { kStageEdgeAgg = 0, kStageEdgeFinal = 1, kStageEdgeReduce = 2, kStageEwma = 3,
              kStagePagerank = 4, kStageTraceStruct = 5, kStageSegments = 6, kStageSummary = 7,
              kStageGroup = 8, kStageEdgeWindows = 9, kStageEdgeWindowKernel = 10,
-             kNumStages = 11 };
+             kStageEdgeLoad = 11, kStageEdgeLoadKernel = 12, kStageEdgeLoadScan = 13,
+             kNumStages = 14 };
 
 // Host wall-clock slots (anomod_ctx_host_ms): the last occurrence of each
 // one-off setup step, or of a call phase the stage events cannot see.
@@ -253,6 +254,10 @@ size_t span_edge_keys_ws_bytes(const anomod_spans* s);
 // the keys from the row stream instead (the exact edge quantiles).
 int span_edge_keys(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, unsigned long long* keys,
                    unsigned long long* ws, bool use_rows = false);
+// Whether the set holds complete parent rows a call may stream now
+// (anomod_spans::parent_row filled, none of the walk overrides of edge_agg.hip
+// set): positions [rows_lo, rows_hi), codes rows_S / rows_S + 1 for root / orphan.
+bool span_rows_ready(const anomod_spans* s);
 // The parent scan the edge kernels use for a grouped set (edge_agg.hip):
 // *unique = the scans from both ends apply (ids declared unique, collector
 // order).  An unknown order hint is probed first, as at the set's first

@@ -1802,6 +1802,8 @@ int edge_aggregate_records(anomod_ctx* ctx, const uint64_t* rec, uint64_t n, uin
   return ANOMOD_OK;
 }
 
+bool span_rows_ready(const anomod_spans* s) { return rows_ready(s); }
+
 int span_scan_choice(anomod_ctx* ctx, const anomod_spans* s, unsigned long long* d_cnt,
                      bool* unique) {
   if (int rc = probe_order(ctx, s, d_cnt)) return rc;

@@ -121,7 +121,9 @@ int anomod_ctx_synchronize(anomod_ctx* ctx);
  * 7 = value summary (select + sort + sum + picks),
  * 8 = trace grouping of an ungrouped span set (radix passes + copy + trace_ptr),
  * 9 = edge-window pass (per-span edge keys + the window kernel),
- * 10 = the window kernel of stage 9 alone.                                  */
+ * 10 = the window kernel of stage 9 alone,
+ * 11 = edge-load pass (keys form: per-span edge keys; the stream kernel; the
+ *      scan), 12 = its stream kernel alone, 13 = its scan alone.            */
 int anomod_ctx_stage_ms(const anomod_ctx* ctx, int stage, double* ms);
 /* Host wall milliseconds of the last occurrence of a one-off setup step or of
  * a call phase the stage events above cannot see, and how many times it
@@ -419,6 +421,55 @@ typedef struct {
 } anomod_edge_windows;
 int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               anomod_edge_windows* out);
+/* Edge load of a grouped set with a start-time column: per (window, edge row)
+ * the time the edge's calls were open inside the window and the calls still
+ * open when the window opens — the saturation signal the start-window tables
+ * above cannot carry (they book a call in the window it starts in only).
+ * Rows, inputs and the "in traces" rule are those of
+ * anomod_edge_windows_spans: S, E = (S + 2) * S, T = n_windows in [1, 65536]
+ * with T * E <= 2^24, t0_us, step_us >= 1.  All integers.  For a span i at a
+ * position inside [trace_ptr[0], trace_ptr[n_traces]):
+ *   s = start_us[i],  e = min(s + dur_us[i], 2^64 - 1)   (saturating add)
+ *   window w = [lo_w, hi_w) = [t0 + w * step, t0 + (w + 1) * step), evaluated
+ *   as if in unbounded integers (t0 + T * step may pass 2^64)
+ * and with cell = w * E + row, row = the edge row the aggregation puts the
+ * span in:
+ *   busy_us[cell] = sum over the row's spans of max(0, min(e, hi_w) - max(s, lo_w))
+ *                   (busy_us / step_us = the mean number of calls in flight)
+ *   carried[cell] = the row's spans with s < lo_w < e: open when the window
+ *                   opens (a span that starts exactly at lo_w is that
+ *                   window's arrival, not carried into it)
+ *   outside       = the spans in traces that add to no cell of either table:
+ *                   dur == 0, e <= t0, or s >= t0 + T * step (and a start
+ *                   of 2^64 - 1, where e saturates onto s)
+ * A span that starts before t0 but reaches into the range is clipped, not
+ * dropped — deliberately unlike `outside` of anomod_edge_windows_spans.
+ * Spans outside every trace are in no cell and not in `outside`.  busy_us
+ * cannot overflow (fewer than 2^32 spans a call, each shorter than 2^32 us);
+ * both tables are additive over any split of the traces, and the call is
+ * rank-local: no collective runs even with a communicator attached.  Every
+ * result is bit-exact for any launch geometry.  The work per span does not
+ * depend on how many windows it covers (difference tables and one scan along
+ * w).  A set that holds its parent rows (a resident set after its first
+ * aggregation) is read as one stream of 18 B a span; any other grouped set
+ * takes its edges from the aggregation's walk first.  The call neither fills
+ * the row column nor changes the set's hints beyond what
+ * anomod_edge_windows_spans does.  Validation and error codes are those of
+ * anomod_edge_windows_spans (ANOMOD_ESTATE without a start column); n == 0
+ * gives zeros; a NULL table is skipped.                                      */
+typedef struct {
+  uint32_t n_services;   /* in : S; E = (S + 2) * S as in anomod_edge_table      */
+  uint32_t n_windows;    /* in : T in [1, 65536], T * E <= 2^24, else EINVAL      */
+  uint64_t t0_us;        /* in                                                   */
+  uint64_t step_us;      /* in : >= 1                                            */
+  uint64_t* busy_us;     /* [T * E], cell = w * E + edge row; may be NULL        */
+  uint64_t* carried;     /* [T * E]; may be NULL                                 */
+  uint64_t outside;      /* out                                                  */
+} anomod_edge_load;
+int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_edge_load* out);
+/* Windows per segment of the edge-load scan along w (tests place T at its
+ * borders).                                                                 */
+uint32_t anomod_edge_load_scan_segment(void);
 /* Per-window edge latency quantiles of a grouped set with a start-time
  * column: the rows and the window rule of anomod_edge_windows_spans (a span
  * outside [0, n_windows) is counted in `outside` and lies in no cell; a span
