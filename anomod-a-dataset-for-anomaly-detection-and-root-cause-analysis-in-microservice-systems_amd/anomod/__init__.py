@@ -22,7 +22,7 @@ from .engine import (Experiment, Features, default_context, fault_target, featur
 from . import api
 from .segments import SegmentSet, service_name_of, trace_infos
 from .writers import jaeger_to_csv, write_jaeger_csv, write_metric_long_csv
-from .spans import (CriticalPath, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
+from .spans import (CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
                     TraceSpectrum, TraceStructure, edge_rows, spectrum_thresholds)
 
 __all__ = [
@@ -37,7 +37,7 @@ __all__ = [
     "SegmentSet", "service_name_of", "trace_infos", "analyze_trace_patterns",
     "jaeger_to_csv", "write_jaeger_csv", "write_metric_long_csv", "decode_native",
     "load_trace_file", "api", "trace_window_scores", "TraceSpectrum", "spectrum_thresholds",
-    "CriticalPath", "TraceShapes", "ErrorOrigins", "EdgeLoad", "load_window_scores",
+    "CriticalPath", "TraceShapes", "ErrorOrigins", "EdgeLoad", "EdgeExemplars", "load_window_scores",
 ]
 
 

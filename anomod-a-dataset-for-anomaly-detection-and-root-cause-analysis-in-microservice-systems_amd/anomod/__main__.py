@@ -1,6 +1,7 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
                                  [--spectrum] [--critical-path] [--shapes]
                                  [--error-origins] [--trace-step S [--trace-load]]
+                                 [--exemplars K]
                                  [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
@@ -16,6 +17,8 @@ from __future__ import annotations
 import argparse
 import json
 import sys
+
+import numpy as np
 
 from . import features, load_experiment, rank
 
@@ -71,6 +74,59 @@ def edge_load_doc(load) -> dict:
             "windows": int(load.n_windows), "outside": int(load.outside), "edges": rows}
 
 
+def _exemplar_calls(ex, spans, row: int, names: dict) -> list[dict]:
+    ids = [names.get(t, t) for t in ex.trace_ids(spans, row)]
+    return [{"trace_id": ids[j], "span_id": f"{int(ex.span_id[row, j]):016x}",
+             "dur_us": int(ex.dur_us[row, j]), "error": bool(int(ex.flags[row, j]) & 1),
+             "start_us": int(ex.start_us[row, j])} for j in range(len(ids))]
+
+
+def exemplars_doc(feats, spans, ranking, top: int = 5, trace_file=None) -> dict:
+    """The "exemplars" object of the features JSON: for each of the `top`
+    ranked services, "slow" — its incoming edge with the largest p99_us and
+    that edge's slowest calls — and "errors" — its incoming edge with the most
+    errors and that edge's slowest failed calls (None when no incoming edge
+    holds a span / an error).  A call is {trace_id, span_id (hex), dur_us,
+    error, start_us}, slowest first.  trace_id is the set's own id
+    (EdgeExemplars.trace_ids); for a set decoded without id strings it is
+    looked up in `trace_file` by its hash, and stays the hash in hex when the
+    file does not hold it."""
+    edges, ex, err_ex = feats.edges, feats.exemplars, feats.error_exemplars
+    S = edges.n_services
+    out = {}
+    picked = []
+    for name, _ in ranking[:top]:
+        c = edges.services.index(name)
+        rows = np.arange(S + 2) * S + c
+        entry = {"slow": None, "errors": None}
+        p99 = np.where(edges.count[rows] > 0, np.nan_to_num(edges.p99_us[rows], nan=-1.0), -1.0)
+        if (p99 >= 0).any():
+            r = int(rows[int(np.argmax(p99))])
+            entry["slow"] = {"parent": edges.parent_name(r // S), "child": name,
+                             "p99_us": float(edges.p99_us[r]),
+                             "calls": (ex, r)}
+        if edges.errors[rows].any():
+            r = int(rows[int(np.argmax(edges.errors[rows]))])
+            entry["errors"] = {"parent": edges.parent_name(r // S), "child": name,
+                               "errors": int(edges.errors[r]),
+                               "calls": (err_ex, r)}
+        out[name] = entry
+        picked += [e["calls"] for e in entry.values() if e is not None]
+    names = {}
+    if spans.trace_ids is None and trace_file is not None:
+        from .decode import trace_ids_by_hash
+
+        hexes = {t for table, r in picked for t in table.trace_ids(spans, r)}
+        names = {f"{h:016x}": s
+                 for h, s in trace_ids_by_hash(trace_file, (int(t, 16) for t in hexes)).items()}
+    for entry in out.values():
+        for e in entry.values():
+            if e is not None:
+                table, r = e["calls"]
+                e["calls"] = _exemplar_calls(table, spans, r, names)
+    return {"k": int(ex.k), "services": out}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m anomod")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -107,6 +163,10 @@ def main(argv=None) -> int:
                    help="also tell the error-flagged spans whose failure started there from "
                         "those that relayed a callee's failure, score services by the failures "
                         "that started in them, and write the counts as \"error_origins\"")
+    f.add_argument("--exemplars", type=int, metavar="K",
+                   help="also list, for each of the top 5 ranked services, the K slowest calls "
+                        "of its slowest incoming edge and the K slowest failed calls of its "
+                        "most failing one, with their trace ids, as \"exemplars\" (K in 1..64)")
     f.add_argument("--baseline", metavar="TRACES",
                    help="trace file (or dir) of a normal run: its features are the baseline "
                         "of the latency term and of the spectrum's latency thresholds")
@@ -132,7 +192,7 @@ def main(argv=None) -> int:
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
                      critical_path=args.critical_path, trace_quantile=args.trace_quantile,
                      shapes=args.shapes, error_origins=args.error_origins,
-                     trace_load=args.trace_load)
+                     trace_load=args.trace_load, exemplars=args.exemplars)
     ranking = rank(feats, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -173,6 +233,9 @@ def main(argv=None) -> int:
         doc["edge_load"] = edge_load_doc(feats.edge_load)
         doc["load_scores"] = dict(zip(feats.edges.services,
                                       map(float, feats.params["components"]["load"])))
+    if feats.exemplars is not None:
+        doc["exemplars"] = exemplars_doc(feats, exp.spans, ranking,
+                                         trace_file=exp.meta.get("trace_file"))
     text = json.dumps(doc, indent=2)
     if args.out:
         with open(args.out, "w") as fh:

@@ -30,7 +30,7 @@ _STATUS = {EINVAL: "EINVAL", EHIP: "EHIP", ERCCL: "ERCCL", ENOMEM: "ENOMEM", EST
 (STAGE_EDGE_AGG, STAGE_EDGE_FINAL, STAGE_EDGE_REDUCE, STAGE_EWMA, STAGE_PAGERANK,
  STAGE_TRACE_STRUCT, STAGE_SEGMENTS, STAGE_SUMMARY, STAGE_GROUP,
  STAGE_EDGE_WINDOWS, STAGE_EDGE_WINDOW_KERNEL, STAGE_EDGE_LOAD, STAGE_EDGE_LOAD_KERNEL,
- STAGE_EDGE_LOAD_SCAN) = range(14)
+ STAGE_EDGE_LOAD_SCAN, STAGE_EDGE_EXEMPLARS, STAGE_EDGE_EXEMPLARS_KERNEL) = range(16)
 (HOST_GROUP_ALLOC, HOST_GROUP_PINNED, HOST_GROUP_WALL, HOST_UPLOAD_SETUP,
  HOST_SET_ALLOC) = range(5)
 HOST_SLOTS = 5
@@ -96,6 +96,21 @@ class EdgeLoadC(C.Structure):
         ("busy_us", C.POINTER(C.c_uint64)),
         ("carried", C.POINTER(C.c_uint64)),
         ("outside", C.c_uint64),
+    ]
+
+
+class EdgeExemplarsC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("k", C.c_uint32),
+        ("which", C.c_uint32),
+        ("n_found", C.POINTER(C.c_uint32)),
+        ("position", C.POINTER(C.c_uint64)),
+        ("trace", C.POINTER(C.c_uint64)),
+        ("span_id", C.POINTER(C.c_uint64)),
+        ("dur_us", C.POINTER(C.c_uint32)),
+        ("flags", C.POINTER(C.c_uint16)),
+        ("start_us", C.POINTER(C.c_uint64)),
     ]
 
 
@@ -254,6 +269,7 @@ _SIGS = {
     "anomod_edge_windows_spans": (_i32, [_vp, _vp, _P(EdgeWindowsC)]),
     "anomod_edge_load_spans": (_i32, [_vp, _vp, _P(EdgeLoadC)]),
     "anomod_edge_load_scan_segment": (C.c_uint32, []),
+    "anomod_edge_exemplars_spans": (_i32, [_vp, _vp, _P(EdgeExemplarsC)]),
     "anomod_edge_window_quantiles_spans": (_i32, [_vp, _vp, _P(EdgeWindowQuantilesC)]),
     "anomod_decoded_start_us": (_i32, [_vp, _P(_u64)]),
     "anomod_spans_set_unique_ids": (_i32, [_vp, C.c_int]),

@@ -558,6 +558,35 @@ def load_trace_file(path, services: list[str] | None = None) -> SpanSet:
     return spans
 
 
+_TRACE_ID_FIELD = re.compile(rb'"(?:traceID|traceId|trace_id)"\s*:\s*"([^"\\]*)"')
+
+
+def trace_ids_by_hash(path, hashes) -> dict[int, str]:
+    """The trace ids of a trace file whose hash64 is among `hashes` (the
+    trace_hash column of a decoded set): {hash: id}.  The native decoders keep
+    no id strings, so the few ids a caller wants to print (exemplar traces)
+    are looked up here: one scan of the file for its trace-id fields, hashing
+    each distinct id once, until every wanted hash is found."""
+    want = {int(h) for h in hashes}
+    found: dict[int, str] = {}
+    if not want or os.path.getsize(path) == 0:
+        return found
+    seen = set()
+    with open(path, "rb") as fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+        for m in _TRACE_ID_FIELD.finditer(mm):
+            raw = m.group(1)
+            if raw in seen:
+                continue
+            seen.add(raw)
+            s = raw.decode("utf-8", "replace")
+            h = hash64(s)
+            if h in want:
+                found[h] = s
+                if len(found) == len(want):
+                    break
+    return found
+
+
 def _load_trace_file_py(data, path, services: list[str] | None = None) -> SpanSet:
     doc = json.loads(data[:])
     if isinstance(doc, dict) and "traces" in doc:

@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import (CriticalPath, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
+from .spans import (CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
                     TraceSpectrum, TraceStructure, edge_rows)
 
 
@@ -466,6 +466,32 @@ class Context:
             self._check(self._lib.anomod_edge_load_spans(self.handle, spans.handle, C.byref(cs)))
             load.outside = int(cs.outside)
             return load
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def edge_exemplars(self, spans: DeviceSpans | SpanSet, k: int = 8,
+                       errors_only: bool = False) -> EdgeExemplars:
+        """The k slowest calls of every edge row of a grouped set
+        (anomod_edge_exemplars_spans), or with errors_only the k slowest
+        error-flagged ones: ordered by dur_us descending, then span position
+        ascending.  EdgeExemplars.trace_ids / .select carry a row's exemplars
+        back to their traces.  k in [1, 64].  Rank-local.  A resident set
+        that has been aggregated is read as one stream (its parent rows); a
+        host set is uploaded for the call.  A start column is not needed."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            if not 1 <= int(k) <= 64 or int(k) * edge_rows(S) > 1 << 24:
+                raise L.AnomodError(L.EINVAL, f"k={k} outside [1, 64] or k * edge rows > 2^24 "
+                                    f"(n_services={S})")
+            ex = EdgeExemplars.empty(spans.services, k, 1 if errors_only else 0)
+            cs = ex.c_struct()
+            self._check(self._lib.anomod_edge_exemplars_spans(self.handle, spans.handle,
+                                                              C.byref(cs)))
+            return ex
         finally:
             if tmp is not None:
                 tmp.free()

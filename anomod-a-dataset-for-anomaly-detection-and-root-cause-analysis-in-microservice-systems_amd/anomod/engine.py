@@ -23,7 +23,7 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import (EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes, TraceSpectrum,
+from .spans import (EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes, TraceSpectrum,
                     edge_rows, spectrum_thresholds)
 
 # --------------------------------------------------------------------------
@@ -178,6 +178,10 @@ class Features:
     error_origins: ErrorOrigins | None = None
     # features(trace_load=True): per-window busy time and carried calls of every edge
     edge_load: EdgeLoad | None = None
+    # features(exemplars=K): the K slowest calls of every edge, and the K
+    # slowest error-flagged ones
+    exemplars: EdgeExemplars | None = None
+    error_exemplars: EdgeExemplars | None = None
 
 
 _default_ctx: Context | None = None
@@ -330,7 +334,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              self_time: bool = False, spectrum: bool = False,
              spectrum_rows: str = "root", critical_path: bool = False,
              trace_quantile: int | None = None, shapes: bool = False,
-             error_origins: bool = False, trace_load: bool = False) -> Features:
+             error_origins: bool = False, trace_load: bool = False,
+             exemplars: int | None = None) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -372,7 +377,11 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     score gains 0.25 * ls / (1 + ls) (components["load"]): calls that stay
     open pile up busy time in every window they last through, which the
     start-window series above cannot see — a hung call is one cell of their
-    latency sum, and none at all on an edge below trace_min_count."""
+    latency sum, and none at all on an edge below trace_min_count.  With
+    exemplars=K (1..64) the result also holds the K slowest calls of every
+    edge and the K slowest error-flagged ones (Context.edge_exemplars:
+    Features.exemplars / .error_exemplars) — the way from a ranked service
+    back to the traces that show it; no score or component changes."""
     if trace_load and trace_step_s is None:
         raise ValueError("features(trace_load=True) needs trace_step_s")
     if trace_quantile is not None and trace_step_s is None:
@@ -453,9 +462,14 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
             nov = census.novelty(exp.spans, baseline.shapes)
             params["components"]["shape_novelty"] = nov
             score = score + 0.25 * nov
+    ex = err_ex = None
+    if exemplars is not None:
+        ex = ctx.edge_exemplars(exp.spans, int(exemplars))
+        err_ex = ctx.edge_exemplars(exp.spans, int(exemplars), errors_only=True)
     if trace_step_s is None:
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
-                        spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins)
+                        spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
+                        exemplars=ex, error_exemplars=err_ex)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count,
                              trace_quantile)
     tsq = ts / (1.0 + ts)  # the metric term's squashing
@@ -475,7 +489,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     return Features(exp.name, edges, Z, series, score, params,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
                     spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
-                    edge_load=load)
+                    edge_load=load, exemplars=ex, error_exemplars=err_ex)
 
 
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,

@@ -377,6 +377,77 @@ class EdgeLoad:
         return MetricMatrix(X, ts, series)
 
 
+U64_MAX = 0xFFFFFFFFFFFFFFFF
+
+
+@dataclass
+class EdgeExemplars:
+    """The k slowest calls of every edge row (anomod_edge_exemplars_spans),
+    all spans (which = 0) or the error-flagged ones (which = 1): row r holds
+    n_found[r] exemplars in slots [r, 0 .. n_found[r]), ordered by dur_us
+    descending, then span position ascending — ties go by position, so the
+    table is a pure function of the set.  An unused slot holds position and
+    trace 2^64 - 1 and zeros elsewhere.  Rows as in EdgeTable."""
+
+    services: list[str]
+    k: int
+    which: int
+    n_found: np.ndarray    # u32 [E]
+    position: np.ndarray   # u64 [E, K] span position
+    trace: np.ndarray      # u64 [E, K] trace index
+    span_id: np.ndarray    # u64 [E, K]
+    dur_us: np.ndarray     # u32 [E, K]
+    flags: np.ndarray      # u16 [E, K]
+    start_us: np.ndarray   # u64 [E, K]; 0 when the set has no start column
+
+    COLUMNS = ("position", "trace", "span_id", "dur_us", "flags", "start_us")
+
+    @staticmethod
+    def empty(services: list[str], k: int, which: int = 0) -> "EdgeExemplars":
+        """The table of a set without spans: nothing found, every slot unused."""
+        shape = (edge_rows(len(services)), int(k))
+        return EdgeExemplars(list(services), int(k), int(which),
+                             np.zeros(shape[0], np.uint32), np.full(shape, U64_MAX, np.uint64),
+                             np.full(shape, U64_MAX, np.uint64), np.zeros(shape, np.uint64),
+                             np.zeros(shape, np.uint32), np.zeros(shape, np.uint16),
+                             np.zeros(shape, np.uint64))
+
+    def c_struct(self) -> L.EdgeExemplarsC:
+        return L.EdgeExemplarsC(
+            len(self.services), self.k, self.which, L.ptr(self.n_found, C.c_uint32),
+            L.ptr(self.position, C.c_uint64), L.ptr(self.trace, C.c_uint64),
+            L.ptr(self.span_id, C.c_uint64), L.ptr(self.dur_us, C.c_uint32),
+            L.ptr(self.flags, C.c_uint16), L.ptr(self.start_us, C.c_uint64))
+
+    def row(self, parent: str, child: str) -> int:
+        """Edge row of (parent service -> child service) by name; parent
+        "ROOT" / "ORPHAN" as EdgeTable.parent_name spells them."""
+        S = len(self.services)
+        p = S if parent == "ROOT" else S + 1 if parent == "ORPHAN" else self.services.index(parent)
+        return p * S + self.services.index(child)
+
+    def trace_indices(self, row: int) -> np.ndarray:
+        """Trace index of each exemplar of the row, slowest first (a trace
+        that holds several of them appears several times)."""
+        return self.trace[row, : int(self.n_found[row])].astype(np.int64)
+
+    def trace_ids(self, spans: SpanSet, row: int) -> list[str]:
+        """Trace id of each exemplar of the row: SpanSet.trace_ids when the
+        set carries them, else the trace_hash of the trace's first span as 16
+        hex digits."""
+        idx = self.trace_indices(row).tolist()
+        if spans.trace_ids is not None:
+            return [spans.trace_ids[t] for t in idx]
+        return [f"{int(spans.trace_hash[int(spans.trace_ptr[t])]):016x}" for t in idx]
+
+    def select(self, spans: SpanSet, row: int) -> SpanSet:
+        """The exemplar traces of the row as a span set (SpanSet.select_traces:
+        whole traces, in trace order)."""
+        mask = np.zeros(spans.n_traces, bool)
+        mask[self.trace_indices(row)] = True
+        return spans.select_traces(mask)
+
+
 @dataclass
 class CriticalPath:
     """Critical path of a span set with start times

@@ -123,7 +123,9 @@ int anomod_ctx_synchronize(anomod_ctx* ctx);
  * 9 = edge-window pass (per-span edge keys + the window kernel),
  * 10 = the window kernel of stage 9 alone,
  * 11 = edge-load pass (keys form: per-span edge keys; the stream kernel; the
- *      scan), 12 = its stream kernel alone, 13 = its scan alone.            */
+ *      scan), 12 = its stream kernel alone, 13 = its scan alone,
+ * 14 = edge-exemplars pass (keys form: per-span edge keys; the stream kernel;
+ *      the gather), 15 = its stream kernel alone.                           */
 int anomod_ctx_stage_ms(const anomod_ctx* ctx, int stage, double* ms);
 /* Host wall milliseconds of the last occurrence of a one-off setup step or of
  * a call phase the stage events above cannot see, and how many times it
@@ -470,6 +472,44 @@ int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_ed
 /* Windows per segment of the edge-load scan along w (tests place T at its
  * borders).                                                                 */
 uint32_t anomod_edge_load_scan_segment(void);
+/* Edge exemplars of a grouped set: the K slowest calls of every edge row, to
+ * be carried back to their traces (SpanSet.trace_ids / select_traces).  All
+ * values are integers and exact.  Rows, the "in traces" rule and the edge of
+ * a span are those of anomod_edge_aggregate_spans / anomod_edge_load_spans:
+ * S, E = (S + 2) * S.  For every edge row e, take the spans of that row at
+ * positions inside [trace_ptr[0], trace_ptr[n_traces]); when which == 1, only
+ * those with ANOMOD_FLAG_ERROR.  Order them by dur_us descending, then by span
+ * position ascending: the first min(K, number of such spans) are the row's
+ * exemplars, in that order, in slots e * K .. e * K + n_found[e] - 1; the
+ * row's other slots are unused.  Ties are part of the contract: they are
+ * decided by position, never by arrival, so the result is a pure function of
+ * the set — it does not depend on launch geometry, workgroup count, the form
+ * the kernel takes or how its atomics interleave.  dur_us of a row's first
+ * slot is the row's max_us.  Every output pointer may be NULL.  A start
+ * column is not required (start_us is 0 without one).  Validation, error
+ * codes and texts are those of anomod_edge_load_spans where they overlap
+ * (grouped set, device, max_svc < S, S in [1, 4096]); n == 0 gives zeros and
+ * the unused-slot values.  At most 2^32 - 2 spans in traces a call, else
+ * ANOMOD_EINVAL.  A set that holds its parent rows is read as one stream of
+ * 10 B a span; any other grouped set takes its edges from the aggregation's
+ * walk first.  The call is rank-local (a caller merges the ranks' lists by
+ * (dur_us descending, rank, position)) and neither fills the row column nor
+ * changes the set's hints beyond what anomod_edge_load_spans does.          */
+typedef struct {
+  uint32_t n_services;  /* in : S, E = (S + 2) * S                                  */
+  uint32_t k;           /* in : K in [1, 64], E * K <= 2^24, else EINVAL             */
+  uint32_t which;       /* in : 0 every span, 1 spans with ANOMOD_FLAG_ERROR; else EINVAL */
+  uint32_t* n_found;    /* [E]     min(K, qualifying spans of the row)               */
+  uint64_t* position;   /* [E * K] span position; 2^64 - 1 in an unused slot         */
+  uint64_t* trace;      /* [E * K] t with trace_ptr[t] <= position < trace_ptr[t+1]; */
+                        /*         2^64 - 1 unused                                   */
+  uint64_t* span_id;    /* [E * K] 0 unused                                          */
+  uint32_t* dur_us;     /* [E * K] 0 unused                                          */
+  uint16_t* flags;      /* [E * K] 0 unused                                          */
+  uint64_t* start_us;   /* [E * K] 0 unused or when the set has no start column      */
+} anomod_edge_exemplars;
+int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                                anomod_edge_exemplars* out);
 /* Per-window edge latency quantiles of a grouped set with a start-time
  * column: the rows and the window rule of anomod_edge_windows_spans (a span
  * outside [0, n_windows) is counted in `outside` and lies in no cell; a span
