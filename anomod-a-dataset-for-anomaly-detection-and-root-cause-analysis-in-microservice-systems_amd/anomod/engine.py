@@ -242,6 +242,12 @@ def _latency_shift(cur: EdgeTable, base: EdgeTable, min_count: int = 10) -> np.n
     return ratio.reshape(S + 2, S).max(axis=0)
 
 
+def _squash(x: np.ndarray) -> np.ndarray:
+    """x / (1 + x), z into [0, 1], with its limit 1 at +inf (inf / inf is NaN)."""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isposinf(x), 1.0, x / (1.0 + x))
+
+
 def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int,
                         cols_per_edge: int = 2) -> np.ndarray:
     """Per-service trace anomaly score from the window scores Z [n,
@@ -249,7 +255,8 @@ def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int,
     quantile column): the first score window is dropped (the EWMA variance
     starts at 0 there), a column scores the mean of its top k =
     max(1, n_left // 20) windows, and a service takes the max over the columns
-    of the edges it is the child of (row % S; ROOT and ORPHAN rows included)."""
+    of the edges it is the child of (row % S; ROOT and ORPHAN rows included);
+    a column whose score is NaN is skipped."""
     out = np.zeros(S)
     Z = np.asarray(Z, np.float64)[1:]
     if Z.shape[0] == 0 or Z.shape[1] == 0:
@@ -258,7 +265,7 @@ def trace_window_scores(Z: np.ndarray, win: EdgeWindows, S: int,
     top = np.sort(Z, axis=0)[-k:].mean(axis=0)
     active = np.nonzero(win.count.sum(axis=0))[0]
     child = np.repeat(active % S, int(cols_per_edge))
-    np.maximum.at(out, child, top[: child.shape[0]])
+    np.fmax.at(out, child, top[: child.shape[0]])
     return out
 
 
@@ -266,7 +273,8 @@ def load_window_scores(Z: np.ndarray, load: EdgeLoad, S: int) -> np.ndarray:
     """Per-service load score from the window scores Z [n, active edges] of
     load.matrix(), by the rule of trace_window_scores: the first score window
     is dropped, a column scores the mean of its top k = max(1, n_left // 20)
-    windows, and a service takes the max over the edges it is the child of."""
+    windows, and a service takes the max over the edges it is the child of
+    (a column whose score is NaN is skipped)."""
     out = np.zeros(S)
     Z = np.asarray(Z, np.float64)[1:]
     if Z.shape[0] == 0 or Z.shape[1] == 0:
@@ -274,7 +282,7 @@ def load_window_scores(Z: np.ndarray, load: EdgeLoad, S: int) -> np.ndarray:
     k = max(1, Z.shape[0] // 20)
     top = np.sort(Z, axis=0)[-k:].mean(axis=0)
     child = load.active_rows() % S
-    np.maximum.at(out, child, top[: child.shape[0]])
+    np.fmax.at(out, child, top[: child.shape[0]])
     return out
 
 
@@ -381,7 +389,9 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     exemplars=K (1..64) the result also holds the K slowest calls of every
     edge and the K slowest error-flagged ones (Context.edge_exemplars:
     Features.exemplars / .error_exemplars) — the way from a ranked service
-    back to the traces that show it; no score or component changes."""
+    back to the traces that show it; no score or component changes.
+    Non-finite window scores: a column whose score is NaN is skipped, +inf
+    squashes to 1, so service_scores stays finite."""
     if trace_load and trace_step_s is None:
         raise ValueError("features(trace_load=True) needs trace_step_s")
     if trace_quantile is not None and trace_step_s is None:
@@ -418,7 +428,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
             by_labels[lb] = -1 if i is None else i
         idx = np.fromiter(map(by_labels.__getitem__, labs), np.int64, len(labs))
         ok = idx >= 0
-        np.maximum.at(metric_score, idx[ok], np.asarray(top, np.float64)[ok])
+        np.fmax.at(metric_score, idx[ok], np.asarray(top, np.float64)[ok])  # skips NaN
     # error rate of the calls each service serves
     cnt = edges.count.reshape(S + 2, S).sum(axis=0).astype(np.float64)
     err = edges.errors.reshape(S + 2, S).sum(axis=0).astype(np.float64)
@@ -436,7 +446,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         lat = _latency_shift(self_edges, baseline.self_edges)
     elif baseline is not None:
         lat = _latency_shift(edges, baseline.edges)
-    ms = metric_score / (1.0 + metric_score)  # squash z into [0, 1)
+    ms = _squash(metric_score)  # squash z into [0, 1]
     score = err_rate + lat + 0.25 * ms
     params = {"W": W, "alpha": alpha, "eps": eps,
               "components": {"error_rate": err_rate, "latency": lat, "metric": ms}}
@@ -472,7 +482,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
                         exemplars=ex, error_exemplars=err_ex)
     win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count,
                              trace_quantile)
-    tsq = ts / (1.0 + ts)  # the metric term's squashing
+    tsq = _squash(ts)  # the metric term's squashing
     params["components"]["trace"] = tsq
     params.update(trace_step_s=trace_step_s, trace_W=trace_W, trace_eps=trace_eps,
                   trace_min_count=trace_min_count)
@@ -482,7 +492,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     load = None
     if trace_load:
         load, ls = _trace_load(exp.spans, ctx, trace_step_s, trace_W, trace_eps)
-        lsq = ls / (1.0 + ls)
+        lsq = _squash(ls)
         params["components"]["load"] = lsq
         params["trace_load"] = True
         score = score + 0.25 * lsq
@@ -495,12 +505,15 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
 def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,
          ctx: Context | None = None) -> list[tuple[str, float]]:
     """Root-cause ranking: personalized PageRank over the caller -> callee
-    graph (weights = call counts), personalization = service anomaly scores."""
+    graph (weights = call counts), personalization = service anomaly scores
+    (a non-finite score counts as 0; the uniform vector only when nothing
+    positive remains)."""
     ctx = ctx or default_context()
     services = feats.edges.services
     row_ptr, col, w = feats.edges.call_graph()
     p = np.asarray(feats.service_scores, np.float64).copy()
-    if not np.isfinite(p).all() or p.sum() <= 0:
+    p = np.where(np.isfinite(p), p, 0.0)
+    if p.sum() <= 0:
         p = np.ones(len(services))
     p = p + 1e-9 * p.sum()  # every node reachable by the restart
     x, _ = ctx.pagerank(row_ptr, col, w, p, alpha=alpha, iters=iters, tol=tol)

@@ -24,6 +24,7 @@ import pytest
 import anomod
 from oracle import native
 
+import engine_ref
 from test_gpu_edge import assert_table_equal
 
 pytestmark = pytest.mark.gpu
@@ -54,14 +55,15 @@ def test_sn_files_to_ranking(ctx, golden, tmp_path):
     Zr = native.ewma_z(mm.X, f.params["alpha"], W, f.params["eps"])
     assert f.window_scores.shape == Zr.shape == (36 // W, 9)
     np.testing.assert_allclose(f.window_scores, Zr, rtol=1e-5, atol=1e-6)
-    # ranking: GPU PageRank == oracle on the call graph and personalization
-    # rank() builds (same restart smoothing)
+    # the score is the model's over the same tables and window scores
+    m = engine_ref.model(engine_ref.inputs_of(exp, f))
+    engine_ref.assert_model_equals(f, m)
+    assert np.isfinite(f.service_scores).all()
+    # ranking: GPU PageRank == oracle on the call graph and the model's
+    # personalization (tests/engine_ref.py: the restart smoothing restated)
     ranking = anomod.rank(f, ctx=ctx)
     row_ptr, col, w = f.edges.call_graph()
-    p = np.asarray(f.service_scores, np.float64).copy()
-    if not np.isfinite(p).all() or p.sum() <= 0:
-        p = np.ones(len(f.edges.services))
-    p = p + 1e-9 * p.sum()
+    p = np.asarray(m["personalization"])
     xr, _ = native.pagerank(row_ptr, col, w, p, 0.85, iters=100, tol=1e-10)
     got = dict(ranking)
     x = np.array([got[s] for s in f.edges.services])
