@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -42,6 +43,37 @@ enum Stage { kStageEdgeAgg = 0, kStageEdgeFinal = 1, kStageEdgeReduce = 2, kStag
 enum HostSlot { kHostGroupAlloc = ANOMOD_HOST_GROUP_ALLOC, kHostGroupPinned = ANOMOD_HOST_GROUP_PINNED,
                 kHostGroupWall = ANOMOD_HOST_GROUP_WALL, kHostUploadSetup = ANOMOD_HOST_UPLOAD_SETUP,
                 kHostSetAlloc = ANOMOD_HOST_SET_ALLOC, kNumHostSlots = ANOMOD_HOST_SLOTS };
+
+// Dense edge stream of a resident set (edge_agg.hip): the layout the set
+// learned from one of its own edge tables — every edge with spans gets a code
+// (its rank among those edges) and the bin range [hist_bin(min), hist_bin(max)]
+// of a cell array — and the u16 code column written through it.  Owned by the
+// set (anomod_spans::dense) and released with it; the device to free on is
+// the one current in free_spans.
+struct DenseSet {
+  enum State { kNone = 0,      // this S was looked at and does not fit (or was rejected)
+               kLearned = 1,   // host layout ready, code column not written yet
+               kCoded = 2 };   // layout on the device, code column written
+  int state = kNone;
+  uint32_t S = 0;              // the service count the layout was learned under
+  uint32_t codes = 0, cells = 0;
+  uint32_t streams = 0;        // row streams at S since the layout was learned
+  int tier = 0;                // 0 = small, 1 = large LDS carve
+  int wgs_per_cu = 0;          // dense kernel workgroups per CU (0: not asked yet)
+  // host layout: 4 words per code {edge, first_bin, base, width}, then the
+  // edge -> code table (u16, 0xFFFF = no code) packed two per word
+  std::vector<uint32_t> host;
+  void* dev = nullptr;         // the same on the device + one flag word
+  size_t dev_bytes = 0;
+  uint16_t* code = nullptr;    // [n_spans]: code | error << 15; 0xFFFF = no span here
+  DenseSet() = default;
+  DenseSet(const DenseSet&) = delete;
+  DenseSet& operator=(const DenseSet&) = delete;
+  ~DenseSet() {
+    if (dev) (void)hipFree(dev);
+    if (code) (void)hipFree(code);
+  }
+};
 
 }  // namespace anomod
 
@@ -144,6 +176,11 @@ struct anomod_spans {
   mutable uint32_t rows_S = 0;
   mutable uint64_t rows_lo = 0, rows_hi = 0;
   bool keep_rows = true;
+  // Dense edge stream (edge_agg.hip): layout and u16 edge-code column, both
+  // functions of the id columns, trace_ptr, svc_flags and the S of the call —
+  // none of which a resident set changes — learned from the set's own table.
+  // Only a set that streams its parent rows ever gets one.
+  mutable std::unique_ptr<anomod::DenseSet> dense;
 };
 
 #define ANOMOD_HIP(ctx, expr)                                                               \

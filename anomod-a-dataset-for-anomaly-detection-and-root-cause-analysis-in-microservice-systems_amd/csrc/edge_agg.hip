@@ -37,7 +37,12 @@
 //  * a resident set is walked once: its first aggregation also stores every
 //    span's parent row (u16, anomod_spans::parent_row), and its later ones
 //    stream svc_flags + dur_us + the row, 10 B/span, into the same tables
-//    (edge_row_kernel) — no ids, no trace bounds, no scan.
+//    (edge_row_kernel) — no ids, no trace bounds, no scan;
+//  * a set whose first table touches few edges and bins (<= 512 edges with
+//    spans, <= 32 Ki bins in their ranges: SN, LONG) also gets a u16 edge-code
+//    column on its fifth aggregation, and from the sixth on streams codes +
+//    dur_us, 6 B/span, into a directly indexed LDS histogram
+//    (edge_dense_kernel) — no hash table.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -67,7 +72,9 @@ static_assert(kPairSlots * 8 == kHtBytes && kCmpSlots * 4 == kHtBytes, "64 KiB t
 constexpr uint32_t kLdsEdges = 512;
 constexpr uint32_t kBins = ANOMOD_HIST_BINS;
 // Experiment-only ablations (never set in the shipped build): 1 = no stats,
-// 2 = no histogram, 4 = no parent lookup, 16 = stream the columns only.
+// 2 = no histogram (3 = neither: the span's values are only kept alive, so the
+// record-based streams still load their columns), 4 = no parent lookup, 16 =
+// stream the columns only (the chunk walk).
 #ifndef ANOMOD_ABL
 #define ANOMOD_ABL 0
 #endif
@@ -332,6 +339,10 @@ __device__ __forceinline__ void stat_add(unsigned char* smem, uint32_t edge, uin
 template <int HT, int ST>
 __device__ __forceinline__ void record(unsigned char* smem, uint32_t edge, uint32_t d, uint32_t fl,
                                        const Table& tab) {
+  if constexpr ((ANOMOD_ABL & 3) == 3) {  // keep the loads, do nothing
+    if ((edge ^ d ^ (fl << 20)) == 0x9E3779B9u) tab.err[0] = d;
+    return;
+  }
   const StatPeek pk = stat_peek<ST>(smem, edge);
   const uint32_t key = edge * kBins + hist_bin(d) + 1u;
   if constexpr ((ANOMOD_ABL & 2) || HT == kHtHbm) {
@@ -1257,6 +1268,211 @@ __global__ __launch_bounds__(kThreads) void edge_row_kernel(
   }
 }
 
+// ---- dense stream: edge codes into a directly indexed histogram -------------
+// A resident set touches a sliver of the E x kBins key space, and its own
+// first table says which: every edge with spans gets a code (its rank among
+// those edges) and the bin range [hist_bin(min), hist_bin(max)] of a cell
+// array (DenseSet, common.h).  Once the set's u16 code column is written
+// (edge_encode_kernel: code | error << 15 by span position, 0xFFFF = no span)
+// an aggregation reads that column and dur_us, 6 B/span, and a span costs one
+// 16-B LDS read of its code's entry {min, max, base - first_bin, first_bin |
+// width << 16} — few distinct addresses, mostly a broadcast —, one ds_add_u32
+// on its cell and the per-code stats of the direct form: no hash, no compare
+// chain, no out-of-line insert.  Correctness never rests on the learned
+// ranges: a span whose bin lies outside its code's range (one unsigned
+// compare) counts in tab.hist in HBM.  Two static LDS carves: small (<= 64
+// codes, <= 8 Ki cells: the SocialNetwork sets) and large (<= 512 codes, <=
+// 32 Ki cells, 4 sum replicas, under 160 KiB).
+constexpr uint32_t kDenseMaxEdges = 1u << 16;  // edge -> code table: at most 128 KiB
+template <int TIER>
+struct DenseCfg;
+template <>
+struct DenseCfg<0> {
+  static constexpr uint32_t kCodes = 64, kCells = 8192, kReps = 8;
+  static constexpr int kLoad = 2;  // load groups (4 spans each) per thread and round
+};
+template <>
+struct DenseCfg<1> {
+  static constexpr uint32_t kCodes = 512, kCells = 32768, kReps = 4;
+  static constexpr int kLoad = 4;
+};
+template <int TIER>
+struct DenseLds {
+  using C = DenseCfg<TIER>;
+  static constexpr int kOffEnt = 0;                                       // u32x4 [kCodes]
+  static constexpr int kOffCell = kOffEnt + (int)C::kCodes * 16;          // u32 [kCells]
+  static constexpr int kOffSum = kOffCell + (int)C::kCells * 4;           // u64 [kCodes][kReps]
+  static constexpr int kOffErr = kOffSum + (int)(C::kCodes * C::kReps) * 8;  // u32 [kCodes]
+  static constexpr int kBytes = kOffErr + (int)C::kCodes * 4;
+  static_assert(kBytes <= 160 * 1024, "LDS budget");
+};
+constexpr int kDenseSmallWgs = 2;  // workgroups per CU of the small carve
+// Plain row streams of a set between the call that learned its layout and the
+// one that writes the code column.  The column is an investment — a pass of
+// its own (8 B/span read, 2 written: about one row stream) and 2 B/span of
+// memory — that only a set which keeps being aggregated repays, so it is made
+// at the set's fifth aggregation: the first four calls of every set run
+// exactly the kernels they ran without the dense stream.
+constexpr uint32_t kDenseAfterStreams = 3;
+template <int LOAD>
+struct DenseRegs {
+  u32x4 dr[LOAD];
+  u32x2 cw[LOAD];
+};
+
+// lay: 4 words per code {edge, first_bin, base, width} (DenseSet::host).
+// (the small carve is held to 64 registers: two workgroups per CU)
+template <int TIER>
+__global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel(
+    const uint32_t* __restrict__ dur, const uint16_t* __restrict__ code,
+    const u32x4* __restrict__ lay, uint32_t ncodes, uint32_t ncells, uint64_t lo, uint64_t hi,
+    Table tab) {
+  using C = DenseCfg<TIER>;
+  using O = DenseLds<TIER>;
+  using Regs = DenseRegs<C::kLoad>;
+  constexpr int kDenseLoad = C::kLoad;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[O::kBytes];
+  const int tid = threadIdx.x;
+  auto* lent = reinterpret_cast<u32x4*>(smem + O::kOffEnt);
+  auto* lent1 = reinterpret_cast<uint32_t*>(smem + O::kOffEnt);
+  auto* lcell = reinterpret_cast<uint32_t*>(smem + O::kOffCell);
+  auto* lsum = reinterpret_cast<unsigned long long*>(smem + O::kOffSum);
+  auto* lerr = reinterpret_cast<uint32_t*>(smem + O::kOffErr);
+  for (uint32_t c = tid; c < ncodes; c += kThreads) {
+    const u32x4 l = lay[c];
+    lent[c] = u32x4{0xFFFFFFFFu, 0u, l.z - l.y, l.y | (l.w << 16)};
+    lerr[c] = 0u;
+  }
+  for (uint32_t k = tid; k < ncells; k += kThreads) lcell[k] = 0u;
+  for (uint32_t k = tid; k < ncodes * C::kReps; k += kThreads) lsum[k] = 0ull;
+  __syncthreads();
+  // cw: code | error << 15.  A code past the layout's (0xFFFF: no span here)
+  // is skipped, so no index below leaves the carve.
+  auto one = [&](uint32_t d, uint32_t cw) {
+    const uint32_t c = cw & 0x7FFFu;
+    if (c >= ncodes) return;
+    if constexpr ((ANOMOD_ABL & 3) == 3) {  // keep the loads, do nothing
+      if ((cw ^ d) == 0x9E3779B9u) tab.err[0] = d;
+      return;
+    }
+    const u32x4 e = lent[c];
+    const uint32_t bin = hist_bin(d);
+    if constexpr (!(ANOMOD_ABL & 2)) {
+      if (bin - (e.w & 0xFFFFu) < (e.w >> 16))
+        atomicAdd(&lcell[e.z + bin], 1u);
+      else
+        atomicAdd(&tab.hist[(uint64_t)lay[c].x * kBins + bin], 1ull);
+    }
+    if constexpr (!(ANOMOD_ABL & 1)) {
+      atomicAdd(&lsum[c * C::kReps + (__lane_id() & (C::kReps - 1u))], (unsigned long long)d);
+      if (d < e.x) atomicMin(&lent1[4u * c], d);
+      if (d > e.y) atomicMax(&lent1[4u * c + 1u], d);
+      if (cw & 0x8000u) atomicAdd(&lerr[c], 1u);
+    }
+  };
+  const uint64_t up = (lo + 3ull) & ~3ull;
+  const uint64_t a0 = up < hi ? up : hi;                      // head [lo, a0)
+  const uint64_t a1 = (hi & ~3ull) > a0 ? (hi & ~3ull) : a0;  // groups [a0, a1), tail [a1, hi)
+  if (blockIdx.x == 0 && tid < 8) {
+    const uint64_t g = tid < 4 ? lo + (uint64_t)tid : a1 + (uint64_t)(tid - 4);
+    if (g < (tid < 4 ? a0 : hi)) one(dur[g], code[g]);
+  }
+  const uint64_t ng = (a1 - a0) / 4;
+  const u32x4* dr4 = reinterpret_cast<const u32x4*>(dur + a0);
+  const u32x2* cw2 = reinterpret_cast<const u32x2*>(code + a0);
+  // groups past the end re-read the last one (no branch around a load) and
+  // take skip codes
+  auto load = [&](uint64_t g0, Regs& R) {
+#pragma unroll
+    for (int j = 0; j < kDenseLoad; ++j) {
+      const uint64_t gi = g0 + (uint64_t)(j * kThreads + tid);
+      const uint64_t gc = gi < ng ? gi : ng - 1;
+      R.dr[j] = dr4[gc];
+      const u32x2 w = cw2[gc];
+      R.cw[j] = gi < ng ? w : u32x2{0xFFFFFFFFu, 0xFFFFFFFFu};
+    }
+  };
+  constexpr uint64_t kPerBlock = (uint64_t)kThreads * kDenseLoad;
+  uint64_t g0 = (uint64_t)blockIdx.x * kPerBlock;
+  Regs cur;
+  if (g0 < ng) load(g0, cur);
+  while (g0 < ng) {
+    const uint64_t gn = g0 + (uint64_t)gridDim.x * kPerBlock;
+    Regs nxt = cur;
+    if (gn < ng) load(gn, nxt);
+#pragma unroll
+    for (int j = 0; j < kDenseLoad; ++j) {
+      one(cur.dr[j].x, cur.cw[j].x & 0xFFFFu);
+      one(cur.dr[j].y, cur.cw[j].x >> 16);
+      one(cur.dr[j].z, cur.cw[j].y & 0xFFFFu);
+      one(cur.dr[j].w, cur.cw[j].y >> 16);
+    }
+    cur = nxt;
+    g0 = gn;
+  }
+  __syncthreads();
+  // Flush: a wave per code, its lanes over the code's cells; then the stats
+  // through code -> edge.  Integer atomics: the tables stay bit-exact.
+  const uint32_t wave = (uint32_t)tid / kWave, lane = (uint32_t)tid % kWave;
+  for (uint32_t c = wave; c < ncodes; c += kWavesPerWG) {
+    const u32x4 l = lay[c];
+    unsigned long long* h = tab.hist + (uint64_t)l.x * kBins + l.y;
+    for (uint32_t k = lane; k < l.w; k += kWave) {
+      const uint32_t cnt = lcell[l.z + k];
+      if (cnt) atomicAdd(&h[k], (unsigned long long)cnt);
+    }
+  }
+  for (uint32_t c = tid; c < ncodes; c += kThreads) {
+    const u32x4 e = lent[c];
+    if (e.x != 0xFFFFFFFFu || e.y != 0u) {
+      const uint32_t edge = lay[c].x;
+      unsigned long long sum = 0;
+      for (uint32_t k = 0; k < C::kReps; ++k) sum += lsum[c * C::kReps + k];
+      atomicAdd(&tab.sum[edge], sum);
+      if (lerr[c]) atomicAdd(&tab.err[edge], (unsigned long long)lerr[c]);
+      atomicMin(&tab.mn[edge], e.x);
+      atomicMax(&tab.mx[edge], e.y);
+    }
+  }
+}
+
+// The code column of spans [lo, hi) from the parent rows and svc_flags through
+// the edge -> code table (e2c, u16 per edge, 0xFFFF = the layout has no code
+// for this edge: *bad is set and the set stays on the row stream).  Four span
+// positions per thread; positions outside [lo, hi) are left alone.
+__global__ __launch_bounds__(256) void edge_encode_kernel(
+    const uint32_t* __restrict__ svcfl, const uint16_t* __restrict__ rows,
+    const uint16_t* __restrict__ e2c, uint16_t* __restrict__ code, uint64_t lo, uint64_t hi,
+    uint32_t S, uint32_t S0, uint32_t* __restrict__ bad) {
+  const uint64_t q0 = lo & ~3ull;
+  const uint64_t nq = (hi - q0 + 3ull) / 4ull;
+  auto enc = [&](uint32_t sf, uint32_t row) -> uint32_t {
+    if (row == 0xFFFFu) return 0xFFFFu;
+    const uint32_t p = row >= S0 ? row - S0 + S : row;
+    const uint32_t c = e2c[p * S + (sf & 0xFFFFu)];
+    if (c == 0xFFFFu) {
+      *bad = 1u;
+      return 0xFFFFu;
+    }
+    return c | ((sf >> 16) & ANOMOD_FLAG_ERROR ? 0x8000u : 0u);
+  };
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq;
+       q += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t g = q0 + 4ull * q;
+    if (g >= lo && g + 4ull <= hi) {
+      const u32x4 sf = *reinterpret_cast<const u32x4*>(svcfl + g);
+      const u32x2 rw = *reinterpret_cast<const u32x2*>(rows + g);
+      u32x2 out;
+      out.x = enc(sf.x, rw.x & 0xFFFFu) | (enc(sf.y, rw.x >> 16) << 16);
+      out.y = enc(sf.z, rw.y & 0xFFFFu) | (enc(sf.w, rw.y >> 16) << 16);
+      *reinterpret_cast<u32x2*>(code + g) = out;
+    } else {
+      for (uint64_t i = g < lo ? lo : g; i < g + 4ull && i < hi; ++i)
+        code[i] = (uint16_t)enc(svcfl[i], rows[i]);
+    }
+  }
+}
+
 // Count + nearest-rank quantiles per edge from the merged histogram: one
 // wave per edge, 14 contiguous bins per lane, wave prefix sum.
 constexpr int kBinsPerLane = (kBins + kWave - 1) / kWave;
@@ -1569,6 +1785,152 @@ int launch_rows(anomod_ctx* ctx, const anomod_spans* s, RowFn fn, uint32_t S, ui
     const uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * (per_cu > 0 ? per_cu : 1), want);
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->svc_flags,
                        s->dur_us, s->parent_row, a, b, S, s->rows_S, E, tab);
+    ANOMOD_HIP(ctx, hipGetLastError());
+  }
+  return ANOMOD_OK;
+}
+
+// ---- dense stream of a resident set (edge_dense_kernel) ---------------------
+// ANOMOD_EDGE_DENSE=0 is the A/B switch; everything that bypasses the parent
+// rows bypasses this too (the callers ask rows_allowed first).
+bool dense_allowed() {
+  const char* f = getenv("ANOMOD_EDGE_DENSE");
+  return !(f && !strcmp(f, "0"));
+}
+
+bool log_kernel() {
+  const char* lg = getenv("ANOMOD_LOG_KERNEL");
+  return lg && lg[0] == '1';
+}
+
+// The set's layout for S from one of its own tables (count / min / max per
+// edge, on the host): codes by edge order, bin ranges back to back in the
+// cell array.  The set is dense when codes <= 512 and cells <= 32 Ki (small
+// carve: <= 64 codes and <= 8 Ki cells); otherwise this S is remembered as
+// not fitting and the set keeps the row stream.  ANOMOD_DENSE_SHRINK=1
+// (tests) narrows every range by one bin at each end, so that the extremes
+// take the kernel's out-of-range path.
+void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned long long* count,
+                 const uint32_t* mn, const uint32_t* mx) {
+  if (!s->dense) s->dense.reset(new DenseSet());
+  DenseSet& d = *s->dense;
+  d.state = DenseSet::kNone;
+  d.S = S;
+  d.codes = d.cells = 0;
+  d.streams = 0;
+  d.wgs_per_cu = 0;
+  d.host.clear();
+  const char* sh = getenv("ANOMOD_DENSE_SHRINK");
+  const bool shrink = sh && !strcmp(sh, "1");
+  uint64_t codes = 0, cells = 0;
+  if (E <= kDenseMaxEdges) {
+    for (uint32_t e = 0; e < E; ++e) {
+      if (!count[e]) continue;
+      uint32_t b0 = hist_bin(mn[e]), b1 = hist_bin(mx[e]);
+      uint32_t width = b1 >= b0 ? b1 - b0 + 1u : 0u;  // (a table merged over ranks: still a range)
+      if (shrink) {
+        b0 += 1u;
+        width = width > 2u ? width - 2u : 0u;
+      }
+      if (codes < DenseCfg<1>::kCodes) {
+        const uint32_t ent[4] = {e, b0, (uint32_t)cells, width};
+        d.host.insert(d.host.end(), ent, ent + 4);
+      }
+      ++codes;
+      cells += width;
+    }
+  }
+  const bool fits = E <= kDenseMaxEdges && codes >= 1 && codes <= DenseCfg<1>::kCodes &&
+                    cells <= DenseCfg<1>::kCells;
+  d.codes = (uint32_t)std::min<uint64_t>(codes, 0xFFFFFFFFull);
+  d.cells = (uint32_t)std::min<uint64_t>(cells, 0xFFFFFFFFull);
+  d.tier = codes <= DenseCfg<0>::kCodes && cells <= DenseCfg<0>::kCells ? 0 : 1;
+  if (fits) {
+    std::vector<uint16_t> e2c(((size_t)E + 1) & ~size_t(1), (uint16_t)0xFFFFu);
+    for (uint32_t c = 0; c < (uint32_t)codes; ++c) e2c[d.host[4u * c]] = (uint16_t)c;
+    const size_t at = d.host.size();
+    d.host.resize(at + e2c.size() / 2);
+    memcpy(d.host.data() + at, e2c.data(), e2c.size() * 2);
+    d.state = DenseSet::kLearned;
+  } else {
+    d.host.clear();
+  }
+  if (log_kernel())  // (tests)
+    fprintf(stderr, "anomod: edge dense layout S=%u codes=%u cells=%u: %s\n", S, d.codes, d.cells,
+            !fits ? "does not fit, the set keeps the row stream" : d.tier ? "large" : "small");
+}
+
+// The transition call of a learned layout.  dense_alloc: device room for the layout and
+// the code column (false: an allocation failed, the set stays on the row
+// stream).  dense_encode: the layout to the device and the code column of
+// [rows_lo, rows_hi), queued after the row stream of this call; the flag word
+// comes back into *h_bad with the table.
+bool dense_alloc(anomod_ctx* ctx, const anomod_spans* s) {
+  DenseSet& d = *s->dense;
+  const size_t bytes = d.host.size() * 4 + 4;
+  if (d.dev_bytes < bytes) {
+    if (d.dev) (void)hipFree(d.dev);
+    d.dev = nullptr;
+    d.dev_bytes = 0;
+    if (dev_malloc(ctx, &d.dev, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      d.dev = nullptr;
+      return false;
+    }
+    d.dev_bytes = bytes;
+  }
+  if (!d.code) {
+    void* p = nullptr;
+    if (dev_malloc(ctx, &p, s->n_spans * 2) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    d.code = static_cast<uint16_t*>(p);
+  }
+  return true;
+}
+
+int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h_bad) {
+  DenseSet& d = *s->dense;
+  auto* base = static_cast<uint32_t*>(d.dev);
+  uint32_t* d_bad = base + d.host.size();
+  ANOMOD_HIP(ctx, hipMemcpyAsync(base, d.host.data(), d.host.size() * 4, hipMemcpyHostToDevice,
+                                 ctx->stream));
+  ANOMOD_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
+  const uint64_t nq = (s->rows_hi - (s->rows_lo & ~3ull) + 3) / 4;
+  if (nq) {
+    const uint64_t blocks = std::min<uint64_t>((nq + 255) / 256, 64ull * ctx->num_cus);
+    hipLaunchKernelGGL(edge_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
+                       s->svc_flags, s->parent_row,
+                       reinterpret_cast<const uint16_t*>(base + 4u * d.codes), d.code, s->rows_lo,
+                       s->rows_hi, S, s->rows_S, d_bad);
+    ANOMOD_HIP(ctx, hipGetLastError());
+  }
+  ANOMOD_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+  return ANOMOD_OK;
+}
+
+// The set's spans [rows_lo, rows_hi) through the dense kernel of its tier, at
+// most max_launch_spans() per launch (u32 cells).
+int launch_dense(anomod_ctx* ctx, const anomod_spans* s, const Table& tab) {
+  DenseSet& d = *s->dense;
+  auto fn = d.tier ? edge_dense_kernel<1> : edge_dense_kernel<0>;
+  if (d.wgs_per_cu <= 0) {  // resident workgroups per CU, asked once per layout
+    int per_cu = 0;
+    ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                        &per_cu, reinterpret_cast<const void*>(fn), kThreads, 0));
+    d.wgs_per_cu = std::max(1, std::min(d.tier == 0 ? kDenseSmallWgs : 1, per_cu));
+  }
+  const int per_cu = d.wgs_per_cu;
+  const uint64_t cap = max_launch_spans();
+  // spans per workgroup round
+  const uint64_t kRound = (uint64_t)kThreads * 4 * (d.tier ? DenseCfg<1>::kLoad : DenseCfg<0>::kLoad);
+  for (uint64_t a = s->rows_lo; a < s->rows_hi; a += cap) {
+    const uint64_t b = std::min<uint64_t>(s->rows_hi, a + cap);
+    const uint64_t want = (b - a + kRound - 1) / kRound;
+    const uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * per_cu, want);
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->dur_us, d.code,
+                       static_cast<const u32x4*>(d.dev), d.codes, d.cells, a, b, tab);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
   return ANOMOD_OK;
@@ -1932,7 +2294,18 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
       build = false;
     }
   }
-  const bool learn = (build || stream) && form < 0 && pair_ok;
+  // Dense stream (edge_dense_kernel).  Whatever call learned a layout for
+  // this S (`build`, or a row stream under another layout's S) is followed by
+  // kDenseAfterStreams plain row streams, then by one that also writes the
+  // code column (`dense_enc`), and from then on the set's aggregations at
+  // this S read codes and durations only (`dense_run`).  A call with another
+  // S goes back to the row stream and learns that S's layout.
+  const bool dense_try = rows_ok && dense_allowed();
+  DenseSet* ds = spans->dense.get();
+  const bool dense_run = stream && dense_try && ds && ds->state == DenseSet::kCoded && ds->S == S;
+  const bool dense_wait = stream && dense_try && ds && ds->state == DenseSet::kLearned && ds->S == S;
+  bool dense_enc = dense_wait && ds->streams >= kDenseAfterStreams;
+  const bool learn = (build || stream) && !dense_run && form < 0 && pair_ok;
   const bool probe = form < 0 && pair_ok && !autof && spans->n_traces > 0 && !learn;
   // the probe's compact form (the forward scan when the order is still unknown)
   const Pick pc = pick_kernel(E, true, uni, kModeNormal, long_set);
@@ -1959,7 +2332,7 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   // (+ 16: the span range of a filled column)
   const size_t small = (L.end_small - L.off_err + 7) & ~size_t(7);
   if (local == ANOMOD_OK) local = ensure_table(ctx, L.bytes);
-  if (local == ANOMOD_OK) local = ensure_host_stage(ctx, small + 16);
+  if (local == ANOMOD_OK) local = ensure_host_stage(ctx, small + 32);  // + the encoder's flag
   if (int rc = comm_agree(ctx, local)) return rc;
   Table tab = table_at(ctx, L, E);
   if (build) tab.bpar = spans->parent_row;
@@ -1985,12 +2358,24 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
                                    hipMemcpyDeviceToHost, ctx->stream));
   }
   if (int rc = stage_begin(ctx, kStageEdgeAgg)) return rc;
-  if (stream) {
-    if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests)
-      fprintf(stderr, "anomod: edge aggregation kernel %s\n", rp.name);
+  auto* h_bad = reinterpret_cast<uint32_t*>(h_range + 2);
+  if (dense_run) {
+    if (log_kernel())  // (tests)
+      fprintf(stderr, "anomod: edge aggregation kernel edge_row_kernel<dense_hist,code_stats>\n");
+    if (int rc = launch_dense(ctx, spans, tab)) return rc;
+  } else if (stream) {
+    if (dense_enc && !dense_alloc(ctx, spans)) {  // no memory: this S stays on the row stream
+      dense_enc = false;
+      ds->state = DenseSet::kNone;
+    }
+    if (log_kernel())  // (tests)
+      fprintf(stderr, "anomod: edge aggregation kernel %s%s\n", rp.name,
+              dense_enc ? " + edge codes" : "");
     Table tr = tab;
     tr.occupancy = learn;
     if (int rc = launch_rows(ctx, spans, rp.fn, S, E, tr)) return rc;
+    if (dense_enc)
+      if (int rc = dense_encode(ctx, spans, S, h_bad)) return rc;
   } else if (spans->n_traces > 0) {
     // A workgroup's LDS counters (histogram slots, errors) are u32 and the
     // dynamic tail may hand one workgroup any share of a launch, so a launch
@@ -2073,7 +2458,18 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   // a compact-form run that reported its fullest workgroup's slots: at most
   // half the pair table's says pair
   if (learn) spans->hist_form = ovf[1] <= kPairSlots / 2 ? 0 : 1;
-  const int ran_ht = stream ? rp.ht : pk.ht;
+  if (dense_enc) {  // an edge without a code (never from this set's own table): row stream
+    ds->state = *h_bad ? DenseSet::kNone : DenseSet::kCoded;
+  } else if (dense_wait) {
+    ++ds->streams;
+  } else if ((build || stream) && dense_try && !dense_run && !(ds && ds->S == S)) {
+    const char* hs = static_cast<const char*>(ctx->h_stage);
+    dense_learn(spans, S, E,
+                reinterpret_cast<const unsigned long long*>(hs + (L.off_count - L.off_err)),
+                reinterpret_cast<const uint32_t*>(hs + (L.off_mn - L.off_err)),
+                reinterpret_cast<const uint32_t*>(hs + (L.off_mx - L.off_err)));
+  }
+  const int ran_ht = dense_run ? -1 : stream ? rp.ht : pk.ht;
   // The set's form from here on: compact when a workgroup of a first
   // aggregation stopped at a saturated pair table, or when more than 1/64 of
   // the spans were counted in HBM past a full one (the set touches more (edge,

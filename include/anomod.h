@@ -187,7 +187,15 @@ int anomod_spans_set_hints(anomod_spans* spans, int scan_order, int hist_form);
  * parents again; unique ids, hints and start times do not affect it.
  * ANOMOD_ESTATE when the set holds none: no aggregation yet, a call run with
  * ANOMOD_PARENT_ROWS=0 / ANOMOD_HIST_FORM / ANOMOD_UNIQUE_SCAN set, an
- * ungrouped set, or the column could not be allocated.                      */
+ * ungrouped set, or the column could not be allocated.
+ * A set that streams its rows may also keep a second derived column, the u16
+ * edge codes of the dense stream (2 B/span more, written by the set's fifth
+ * aggregation at a service count when the edges and histogram bins its first
+ * table touched fit a directly indexed LDS histogram: at most 512 edges with
+ * spans and 32 Ki bins in their ranges); its aggregations from the sixth on
+ * then read codes and durations, 6 B/span.  Same tables bit for bit;
+ * ANOMOD_EDGE_DENSE=0 switches it off, everything that bypasses the rows
+ * bypasses it, and this column keeps its encoding and every other reader.   */
 int anomod_spans_parent_rows(anomod_ctx* ctx, const anomod_spans* spans, uint16_t* out_host,
                              uint32_t n_services);
 /* Copy a host span set to HBM.  Replaces the in-memory hand-off between
