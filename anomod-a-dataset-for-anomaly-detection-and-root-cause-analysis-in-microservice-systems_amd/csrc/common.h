@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <memory>
 #include <string>
 #include <vector>
@@ -17,6 +18,11 @@ namespace anomod {
 // Error plumbing: a per-thread message for ctx-less failures, a per-ctx one
 // otherwise (anomod_last_error).
 void set_error(anomod_ctx* ctx, const char* fmt, ...);
+// ANOMOD_LOG_KERNEL=1 (tests, timing): a call names the kernels it picked on stderr.
+inline bool log_kernel() {
+  const char* lg = getenv("ANOMOD_LOG_KERNEL");
+  return lg && lg[0] == '1';
+}
 
 struct GroupWs;   // group.hip
 struct Uploader;  // upload.hip

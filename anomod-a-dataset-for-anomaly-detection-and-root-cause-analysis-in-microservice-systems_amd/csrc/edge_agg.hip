@@ -1798,11 +1798,6 @@ bool dense_allowed() {
   return !(f && !strcmp(f, "0"));
 }
 
-bool log_kernel() {
-  const char* lg = getenv("ANOMOD_LOG_KERNEL");
-  return lg && lg[0] == '1';
-}
-
 // The set's layout for S from one of its own tables (count / min / max per
 // edge, on the host): codes by edge order, bin ranges back to back in the
 // cell array.  The set is dense when codes <= 512 and cells <= 32 Ki (small

@@ -23,15 +23,11 @@
 //     so a span whose key is below a read of it — however stale — is skipped
 //     after that one read: in steady state almost every span.
 //
-// edge_exemplars_kernel is a persistent stream over span positions in the
-// shape of edge_load_kernel (512 threads, one contiguous range per workgroup,
-// 16-B non-temporal loads, 2048 spans per iteration), with its two sources:
-//   rows  complete parent rows (anomod_spans::parent_row): row 2 B, svc|flags
-//         4 B, dur 4 B = 10 B/span in one pass
-//   keys  any other grouped set: span_edge_keys writes edge << 32 | dur by
-//         span position, then key 8 B (+ svc|flags 4 B when only error spans
-//         are wanted: the key carries no error bit)
-// and two placements of the lists, picked on the host from E * K * 8:
+// edge_exemplars_kernel is the shared edge stream (edge_stream.h) in both of
+// its forms: rows (row 2 B, svc|flags 4 B, dur 4 B = 10 B/span in one pass) and
+// keys (key 8 B after span_edge_keys, + svc|flags 4 B when only error spans are
+// wanted: the key carries no error bit), and two placements of the lists,
+// picked on the host from E * K * 8:
 //   lds     workgroup-private lists in LDS; at the end the workgroup pushes
 //           each non-empty entry through the same cascade on the global lists
 //   global  the cascade runs on the global lists (they stay in L2); the
@@ -42,26 +38,17 @@
 // a position, looks the span's columns up, finds its trace by binary search in
 // trace_ptr and writes the output columns.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
-#include "common.h"
-#include "walk.h"
+#include "edge_stream.h"
 
 namespace anomod {
 namespace {
 
-constexpr int kExThreads = 512;
-constexpr int kExBatch = kExThreads * 4;              // spans per workgroup iteration
+constexpr int kExThreads = 512;                       // 2048 spans per workgroup iteration
 constexpr uint32_t kExLdsBudget = 40u * 1024u - 64u;  // four workgroups per CU
-constexpr uint64_t kExMaxRange = 1ull << 31;          // spans per workgroup (u32 counter)
 constexpr uint64_t kExMaxSpans = 0xFFFFFFFEull;       // spans in traces per call
-constexpr uint32_t kNoEdge = 0xFFFFFFFFu;
 constexpr int kGatherThreads = 256;
-
-using u64x2 = unsigned long long __attribute__((ext_vector_type(2)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
 
 enum { kSrcRows = 0, kSrcKeys = 1 };
 enum { kListsGlobal = 0, kListsGlobalCached = 1, kListsLds = 2 };
@@ -71,7 +58,7 @@ struct ExArgs {
   const uint16_t* rows;            // rows form: [n] parent rows
   const uint32_t* svcfl;           // [n] svc | flags << 16 (rows form; keys form when errors)
   const uint32_t* dur;             // rows form: [n]
-  uint64_t begin, n, per_wg;       // spans [begin, n) lie in traces; per_wg: a multiple of kExBatch
+  uint64_t begin, n, per_wg;       // spans [begin, n) lie in traces; per_wg: a multiple of the batch
   uint32_t E, K;
   uint32_t S, S0;                  // rows form: the call's S, the S the rows were written with
   uint32_t errors;                 // 1: only spans with ANOMOD_FLAG_ERROR
@@ -125,88 +112,31 @@ __global__ __launch_bounds__(kExThreads) void edge_exemplars_kernel(ExArgs a) {
   for (uint32_t c = tid; c < cells; c += kExThreads) l64[c] = 0ull;
   __syncthreads();
 
-  const uint64_t lo = (uint64_t)blockIdx.x * a.per_wg;
-  const uint64_t hi = lo + a.per_wg < a.n ? lo + a.per_wg : a.n;
+  using Lanes = stream::Lanes<kExThreads, SRC == kSrcRows ? 4 : 2>;
+  uint64_t lo, hi;
+  stream::wg_range(a.per_wg, a.n, &lo, &hi);
   uint32_t bad = 0;
-  for (uint64_t b = lo; b < hi; b += kExBatch) {
-    uint64_t pos[4];
-    uint32_t edge[4], dur[4], sf[4];
-    bool live[4];
+  for (uint64_t b = lo; b < hi; b += Lanes::kBatch) {
+    Lanes L(b, hi, a.begin, tid);
+    uint32_t edge[4], dur[4], sf[4] = {0u, 0u, 0u, 0u};
     if constexpr (SRC == kSrcRows) {
-      // four consecutive spans a lane: 16 B of svc|flags, 16 B of durations, 8 B of rows
-      uint32_t row[4];
-      const uint64_t i0 = b + (uint64_t)tid * 4;
-      if (b + kExBatch <= hi) {  // (b is a multiple of kExBatch: aligned groups)
-        const u32x4 f = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.svcfl + i0));
-        const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.dur + i0));
-        const u32x2 r = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.rows + i0));
-        sf[0] = f.x, sf[1] = f.y, sf[2] = f.z, sf[3] = f.w;
-        dur[0] = d.x, dur[1] = d.y, dur[2] = d.z, dur[3] = d.w;
-        row[0] = r.x & 0xFFFFu, row[1] = r.x >> 16, row[2] = r.y & 0xFFFFu, row[3] = r.y >> 16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) live[j] = i0 + j >= a.begin;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint64_t i = i0 + j;
-          live[j] = i < hi && i >= a.begin;
-          sf[j] = live[j] ? a.svcfl[i] : 0u;
-          dur[j] = live[j] ? a.dur[i] : 0u;
-          row[j] = live[j] ? (uint32_t)a.rows[i] : 0u;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pos[j] = i0 + j;
-        // root / orphan codes of the aggregation that wrote the rows -> this call's
-        const uint32_t p = row[j] >= a.S0 ? row[j] - a.S0 + a.S : row[j];
-        const uint32_t svc = sf[j] & 0xFFFFu;
-        edge[j] = p < a.S + ANOMOD_ROOT_ROWS && svc < a.S ? p * a.S + svc : kNoEdge;
-      }
+      stream::load_rows(L, a.rows, a.svcfl, a.dur, a.S, a.S0, edge, dur, sf);
+    } else if (a.errors) {  // (uniform) the key carries no error bit
+      stream::load_keys(L, a.keys, edge, dur, a.svcfl, sf);
     } else {
-      unsigned long long key[4];
-      if (b + kExBatch <= hi) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const uint64_t i = b + ((uint64_t)j * kExThreads + tid) * 2;
-          const u64x2 k = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.keys + i));
-          key[2 * j] = k.x, key[2 * j + 1] = k.y;
-          sf[2 * j] = sf[2 * j + 1] = 0u;
-          if (a.errors) {  // (uniform)
-            const u32x2 f = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.svcfl + i));
-            sf[2 * j] = f.x, sf[2 * j + 1] = f.y;
-          }
-          live[2 * j] = i >= a.begin;
-          live[2 * j + 1] = i + 1 >= a.begin;
-          pos[2 * j] = i, pos[2 * j + 1] = i + 1;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint64_t i = b + ((uint64_t)(j >> 1) * kExThreads + tid) * 2 + (j & 1);
-          live[j] = i < hi && i >= a.begin;
-          key[j] = live[j] ? a.keys[i] : 0ull;
-          sf[j] = live[j] && a.errors ? a.svcfl[i] : 0u;
-          pos[j] = i;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        edge[j] = (uint32_t)(key[j] >> 32);
-        dur[j] = (uint32_t)key[j];
-      }
+      stream::load_keys(L, a.keys, edge, dur);
     }
     unsigned long long x[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       x[j] = 0ull;  // 0: nothing to insert
-      if (!live[j]) continue;
+      if (!L.live[j]) continue;
       if (edge[j] >= E) {  // never for rows of the aggregation / keys of span_edge_keys
         ++bad;
         continue;
       }
       if (a.errors && !((sf[j] >> 16) & ANOMOD_FLAG_ERROR)) continue;
-      x[j] = (unsigned long long)dur[j] << 32 | (0xFFFFFFFFull - (pos[j] - a.begin));
+      x[j] = (unsigned long long)dur[j] << 32 | (0xFFFFFFFFull - (L.pos(j) - a.begin));
     }
     if (a.place == kListsLds) {  // (uniform)
       // the four thresholds are read before the first cascade (one LDS latency
@@ -245,8 +175,7 @@ __global__ __launch_bounds__(kExThreads) void edge_exemplars_kernel(ExArgs a) {
       if (x > peek<AG>(g + K - 1u)) cascade<AG>(g, K, x);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) bad += (uint32_t)__shfl_xor((int)bad, o);
-  if ((tid & 63u) == 0 && bad) atomicAdd(a.misc, (unsigned long long)bad);
+  stream::count_add(a.misc, bad, tid);
 }
 
 struct GatherArgs {
@@ -303,17 +232,6 @@ __global__ __launch_bounds__(kGatherThreads) void edge_exemplars_gather_kernel(G
   a.o_start[c] = start;
 }
 
-// Value of a numeric environment cap, "no cap" when unset or not a number;
-// ANOMOD_EXEMPLARS_WGS must be at least 1.
-uint64_t ex_env_cap(const char* name) {
-  const char* e = getenv(name);
-  if (!e || !*e) return 0xFFFFFFFFull;
-  char* end = nullptr;
-  const unsigned long long v = strtoull(e, &end, 10);
-  if (*end) return 0xFFFFFFFFull;
-  return !strcmp(name, "ANOMOD_EXEMPLARS_WGS") && v == 0 ? 1 : (uint64_t)v;
-}
-
 }  // namespace
 }  // namespace anomod
 
@@ -330,15 +248,8 @@ int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
   ANOMOD_REQUIRE(ctx, K >= 1 && K <= 64, "k=%u outside [1, 64]", K);
   ANOMOD_REQUIRE(ctx, out->which <= 1, "which=%u: 0 (every span) or 1 (error spans)", out->which);
   ANOMOD_REQUIRE(ctx, (uint64_t)E * K <= (1ull << 24), "edge rows * k = %u * %u > 2^24", E, K);
-  ANOMOD_REQUIRE(ctx, spans->device == ctx->device, "span set lives on another device");
-  ANOMOD_REQUIRE(ctx, spans->grouped, "span set is not grouped by trace: anomod_spans_group first");
-  ANOMOD_REQUIRE(ctx, spans->n_spans == 0 || spans->max_svc < S,
-                 "span service index %u >= n_services %u", spans->max_svc, S);
-  uint64_t in_traces[2];
-  if (spans->n_traces && spans->n_spans)
-    if (int rc = bind(ctx)) return rc;
-  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
-  const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
+  uint64_t in_traces[2], n = 0;
+  if (int rc = stream_set_args(ctx, spans, S, false, ANOMOD_EINVAL, in_traces, &n)) return rc;
   const uint64_t EK = (uint64_t)E * K;
   if (n == 0) {
     if (out->n_found) memset(out->n_found, 0, (size_t)E * 4);
@@ -353,41 +264,30 @@ int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
   ANOMOD_REQUIRE(ctx, in_traces[1] - in_traces[0] <= kExMaxSpans,
                  "edge exemplars: %llu spans in traces, at most 2^32 - 2 = %llu a call",
                  (unsigned long long)(in_traces[1] - in_traces[0]), (unsigned long long)kExMaxSpans);
-  // the rows form: complete parent rows over exactly the spans in traces
-  const bool rows = span_rows_ready(spans) && spans->rows_lo == in_traces[0] &&
-                    spans->rows_hi == in_traces[1];
+  EdgeSource src(spans, in_traces, n);
   // One workspace in the windowed table's slot: (keys form: keys | the key
   // walk's words |) misc + the lists + n_found (zeroed together) | the gathered
   // columns.
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t b_keys = rows ? 0 : al(n * 8);
-  const size_t b_ws = rows ? 0 : al(span_edge_keys_ws_bytes(spans));
-  const size_t b_u64 = al(EK * 8), b_u32 = al(EK * 4), b_u16 = al(EK * 2), b_nf = al((size_t)E * 4);
+  const size_t b_u64 = Carve::al(EK * 8), b_u32 = Carve::al(EK * 4), b_u16 = Carve::al(EK * 2),
+               b_nf = Carve::al((size_t)E * 4);
   const size_t b_zero = 256 + b_u64 + b_nf;
   const size_t b_cols = 4 * b_u64 + b_u32 + b_u16;
   char* w = nullptr;
-  if (int rc = ensure_scratch(ctx, kScratchEdgeWindows, b_keys + b_ws + b_zero + b_cols,
+  if (int rc = ensure_scratch(ctx, kScratchEdgeWindows, src.b_keys + src.b_ws + b_zero + b_cols,
                               reinterpret_cast<void**>(&w)))
     return rc;
-  auto* keys = reinterpret_cast<unsigned long long*>(w);
-  auto* ws = reinterpret_cast<unsigned long long*>(w + b_keys);
-  char* t = w + b_keys + b_ws;
-  auto take = [&](size_t bytes) {
-    char* p = t;
-    t += bytes;
-    return p;
-  };
+  Carve cv{w + src.b_keys + src.b_ws};
   ExArgs a{};
-  a.misc = reinterpret_cast<unsigned long long*>(take(256));
-  a.lists = reinterpret_cast<unsigned long long*>(take(b_u64));
+  a.misc = cv.take<unsigned long long>(256);
+  a.lists = cv.take<unsigned long long>(b_u64);
   GatherArgs g{};
-  g.n_found = reinterpret_cast<uint32_t*>(take(b_nf));
-  g.position = reinterpret_cast<uint64_t*>(take(b_u64));
-  g.trace = reinterpret_cast<uint64_t*>(take(b_u64));
-  g.o_span_id = reinterpret_cast<uint64_t*>(take(b_u64));
-  g.o_start = reinterpret_cast<uint64_t*>(take(b_u64));
-  g.o_dur = reinterpret_cast<uint32_t*>(take(b_u32));
-  g.o_flags = reinterpret_cast<uint16_t*>(take(b_u16));
+  g.n_found = cv.take<uint32_t>(b_nf);
+  g.position = cv.take<uint64_t>(b_u64);
+  g.trace = cv.take<uint64_t>(b_u64);
+  g.o_span_id = cv.take<uint64_t>(b_u64);
+  g.o_start = cv.take<uint64_t>(b_u64);
+  g.o_dur = cv.take<uint32_t>(b_u32);
+  g.o_flags = cv.take<uint16_t>(b_u16);
   g.lists = a.lists;
   g.misc = a.misc;
   g.trace_ptr = spans->trace_ptr;
@@ -400,12 +300,10 @@ int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
   g.n_traces = spans->n_traces;
   g.EK = (uint32_t)EK;
   g.K = K;
-  if (rows) {
+  if (src.rows) {
     a.rows = spans->parent_row;
     a.dur = spans->dur_us;
     a.S0 = spans->rows_S;
-  } else {
-    a.keys = keys;
   }
   a.svcfl = spans->svc_flags;
   a.begin = in_traces[0];
@@ -417,28 +315,22 @@ int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
   // (tests, A/B: a smaller LDS budget — 0 = the lists in global memory, no
   // threshold cache — and fewer workgroups, so that small sets give a
   // workgroup several batches and several workgroups meet on a list)
-  const uint64_t budget = std::min<uint64_t>(kExLdsBudget, ex_env_cap("ANOMOD_EXEMPLARS_LDS"));
+  const uint64_t budget = std::min<uint64_t>(kExLdsBudget, env_cap("ANOMOD_EXEMPLARS_LDS"));
   a.place = EK * 8 <= budget ? kListsLds : (uint64_t)E * 8 <= budget ? kListsGlobalCached
                                                                       : kListsGlobal;
   const size_t lds = a.place == kListsLds ? EK * 8 : a.place == kListsGlobalCached ? E * 8u : 0;
-  auto fn = rows ? edge_exemplars_kernel<kSrcRows> : edge_exemplars_kernel<kSrcKeys>;
-  int per_cu = 0;
-  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                      &per_cu, reinterpret_cast<const void*>(fn), kExThreads, lds));
-  // persistent workgroups, one contiguous range of whole batches each
-  const uint64_t batches = (n + kExBatch - 1) / kExBatch;
-  uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * (per_cu > 0 ? per_cu : 1), batches);
-  grid = std::min<uint64_t>(grid, ex_env_cap("ANOMOD_EXEMPLARS_WGS"));
-  a.per_wg = (batches + grid - 1) / grid * kExBatch;
-  if (a.per_wg > kExMaxRange) a.per_wg = kExMaxRange;  // (more workgroups than are resident)
-  grid = (n + a.per_wg - 1) / a.per_wg;
-  if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests, timing)
+  auto fn = src.rows ? edge_exemplars_kernel<kSrcRows> : edge_exemplars_kernel<kSrcKeys>;
+  uint64_t grid = 0;
+  if (int rc = stream_geometry(ctx, fn, kExThreads, lds, n, "ANOMOD_EXEMPLARS_WGS", &a.per_wg,
+                               &grid))
+    return rc;
+  if (log_kernel())  // (tests, timing)
     fprintf(stderr, "anomod: edge exemplars kernel edge_exemplars_kernel<%s>, lists %s\n",
-            rows ? "rows" : "keys", a.place == kListsLds ? "lds" : "global");
+            src.rows ? "rows" : "keys", a.place == kListsLds ? "lds" : "global");
   if (int rc = stage_begin(ctx, kStageEdgeExemplars)) return rc;
   ANOMOD_HIP(ctx, hipMemsetAsync(a.misc, 0, b_zero, ctx->stream));
-  if (!rows)
-    if (int rc = span_edge_keys(ctx, spans, S, keys, ws)) return rc;
+  if (int rc = src.fill(ctx, spans, S, w)) return rc;
+  a.keys = src.keys;
   if (int rc = stage_begin(ctx, kStageEdgeExemplarsKernel)) return rc;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kExThreads), lds, ctx->stream, a);
   ANOMOD_HIP(ctx, hipGetLastError());
@@ -448,23 +340,15 @@ int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
                      dim3(kGatherThreads), 0, ctx->stream, g);
   ANOMOD_HIP(ctx, hipGetLastError());
   if (int rc = stage_end(ctx, kStageEdgeExemplars)) return rc;
-  unsigned long long misc[2] = {0ull, 0ull};
-  ANOMOD_HIP(ctx, hipMemcpyAsync(misc, a.misc, 16, hipMemcpyDeviceToHost, ctx->stream));
-  auto back = [&](void* dst, const void* src, size_t bytes) {
-    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-  };
-  ANOMOD_HIP(ctx, back(out->n_found, g.n_found, (size_t)E * 4));
-  ANOMOD_HIP(ctx, back(out->position, g.position, EK * 8));
-  ANOMOD_HIP(ctx, back(out->trace, g.trace, EK * 8));
-  ANOMOD_HIP(ctx, back(out->span_id, g.o_span_id, EK * 8));
-  ANOMOD_HIP(ctx, back(out->dur_us, g.o_dur, EK * 4));
-  ANOMOD_HIP(ctx, back(out->flags, g.o_flags, EK * 2));
-  ANOMOD_HIP(ctx, back(out->start_us, g.o_start, EK * 8));
-  ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (misc[0]) {
-    set_error(ctx, "edge exemplars: %llu spans carry no edge row (internal error)", misc[0]);
-    return ANOMOD_ESTATE;
-  }
+  ANOMOD_HIP(ctx, stream_back(ctx, out->n_found, g.n_found, (size_t)E * 4));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->position, g.position, EK * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->trace, g.trace, EK * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->span_id, g.o_span_id, EK * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->dur_us, g.o_dur, EK * 4));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->flags, g.o_flags, EK * 2));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->start_us, g.o_start, EK * 8));
+  unsigned long long misc[2];
+  if (int rc = stream_finish(ctx, a.misc, 0, "edge exemplars", "row", misc)) return rc;
   if (misc[1]) {
     set_error(ctx, "edge exemplars: %llu list entries name no span of the set (internal error)",
               misc[1]);

@@ -20,42 +20,26 @@
 // product fits u64.  Nothing ever forms t0 + T * step: every comparison is a
 // quotient against T or an offset inside one window.
 //
-// edge_load_kernel is a persistent stream over span positions in the shape of
-// edge_windows_kernel (512 threads, one contiguous range per workgroup, 16-B
-// non-temporal loads, 2048 spans per iteration), with two sources of the edge
-// row:
-//   rows  the set holds complete parent rows (anomod_spans::parent_row): row
-//         2 B, svc|flags 4 B, dur 4 B, start 8 B = 18 B/span in one pass
-//   keys  any other grouped set: span_edge_keys (the aggregation's own walk)
-//         writes edge << 32 | dur by span position, then key 8 B + start 8 B;
-//         the row column is not filled from here
-// The head partial (window a) goes through a sliding LDS ring of Wt windows x
-// E cells, one u64 a cell, anchored and flushed as in edge_windows.hip; a cell
-// outside the tile, the tail partial and the four difference adds go to global
-// atomics, so correctness never depends on the hit rate (Wt = 0: all global).
+// edge_load_kernel is the shared edge stream (edge_stream.h) in both of its
+// forms: rows (row 2 B, svc|flags 4 B, dur 4 B, start 8 B = 18 B/span in one
+// pass) and keys (key 8 B + start 8 B after span_edge_keys).  The head partial
+// (window a) goes through the stream's sliding LDS window ring, one u64 a cell;
+// a cell outside the tile, the tail partial and the four difference adds go to
+// global atomics, so correctness never depends on the hit rate (Wt = 0: all
+// global).
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
-#include "common.h"
-#include "walk.h"
+#include "edge_stream.h"
 
 namespace anomod {
 namespace {
 
-constexpr int kLoadThreads = 512;
-constexpr int kLoadPairs = 2;                              // two-span loads per lane per batch
-constexpr int kLoadBatch = kLoadThreads * kLoadPairs * 2;  // spans per workgroup iteration
-constexpr uint32_t kLoadLdsBudget = 40u * 1024u - 64u;     // four workgroups per CU (+ s_min)
-constexpr uint64_t kLoadMaxRange = 1ull << 31;             // spans per workgroup (u32 counters)
-constexpr uint32_t kNoWin = 0xFFFFFFFFu;
+constexpr int kLoadThreads = 512;                       // 2048 spans per workgroup iteration
+constexpr uint32_t kLoadLdsBudget = 40u * 1024u - 64u;  // four workgroups per CU (+ the ring's minima)
 constexpr uint32_t kLoadSeg = 256;  // windows per scan segment (anomod_edge_load_scan_segment)
 constexpr int kScanThreads = 256;
 constexpr int kScanChunk = 8;  // windows a scan thread loads before it adds and stores
-
-using u64x2 = unsigned long long __attribute__((ext_vector_type(2)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
-using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
 
 enum { kSrcRows = 0, kSrcKeys = 1 };
 
@@ -65,7 +49,7 @@ struct LoadArgs {
   const uint32_t* svcfl;           //            [n] svc | flags << 16
   const uint32_t* dur;             //            [n]
   const uint64_t* start;           // [n]
-  uint64_t begin, n, per_wg;       // spans [begin, n) lie in traces; per_wg: a multiple of kLoadBatch
+  uint64_t begin, n, per_wg;       // spans [begin, n) lie in traces; per_wg: a multiple of the batch
   uint64_t t0, step;
   uint32_t T, E, Wt;
   uint32_t S, S0;                  // rows form: the call's S, the S the rows were written with
@@ -79,16 +63,16 @@ extern __shared__ __align__(16) unsigned char load_lds[];
 
 template <int SRC>
 __global__ __launch_bounds__(kLoadThreads) void edge_load_kernel(LoadArgs a) {
-  const uint32_t E = a.E, Wt = a.Wt, T = a.T;
-  const uint32_t cells = Wt * E;
+  using Lanes = stream::Lanes<kLoadThreads, SRC == kSrcRows ? 4 : 2>;
+  const uint32_t E = a.E, T = a.T;
+  const uint32_t cells = a.Wt * E;
   auto* l_busy = reinterpret_cast<unsigned long long*>(load_lds);
-  __shared__ uint32_t s_min[3];
   const uint32_t tid = threadIdx.x;
+  stream::WindowRing ring{a.Wt};
   for (uint32_t c = tid; c < cells; c += kLoadThreads) l_busy[c] = 0ull;
-  if (tid < 3) s_min[tid] = kNoWin;
+  ring.init(tid);
   __syncthreads();
 
-  // window `w` of the tile [base, base + Wt) lives in slot (slot0 + w - base) mod Wt
   auto flush_slot = [&](uint32_t slot, uint32_t w) {
     for (uint32_t e = tid; e < E; e += kLoadThreads) {
       const uint32_t c = slot * E + e;
@@ -99,88 +83,28 @@ __global__ __launch_bounds__(kLoadThreads) void edge_load_kernel(LoadArgs a) {
     }
   };
 
-  const uint64_t lo = (uint64_t)blockIdx.x * a.per_wg;
-  const uint64_t hi = lo + a.per_wg < a.n ? lo + a.per_wg : a.n;
-  bool anchored = false;
-  uint32_t base = 0, slot0 = 0;
+  uint64_t lo, hi;
+  stream::wg_range(a.per_wg, a.n, &lo, &hi);
   uint32_t outside = 0, bad = 0;
   uint32_t it = 0;
-  for (uint64_t b = lo; b < hi; b += kLoadBatch, ++it) {
-    uint64_t st[kLoadPairs * 2];
-    uint32_t edge[kLoadPairs * 2], dur[kLoadPairs * 2];
-    bool live[kLoadPairs * 2];
+  for (uint64_t b = lo; b < hi; b += Lanes::kBatch, ++it) {
+    Lanes L(b, hi, a.begin, tid);
+    uint64_t st[4];
+    uint32_t edge[4], dur[4];
     if constexpr (SRC == kSrcRows) {
-      uint32_t row[kLoadPairs * 2], sf[kLoadPairs * 2];
-      // four consecutive spans a lane: 16 B of svc|flags, 16 B of durations,
-      // 8 B of rows and two 16-B loads of start times
-      static_assert(kLoadPairs == 2, "the rows form loads four spans a lane");
-      const uint64_t i0 = b + (uint64_t)tid * 4;
-      if (b + kLoadBatch <= hi) {  // (b is a multiple of kLoadBatch: aligned groups)
-        const u64x2 s0 = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.start + i0));
-        const u64x2 s1 = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.start + i0 + 2));
-        const u32x4 f = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.svcfl + i0));
-        const u32x4 d = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.dur + i0));
-        const u32x2 r = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.rows + i0));
-        st[0] = s0.x, st[1] = s0.y, st[2] = s1.x, st[3] = s1.y;
-        sf[0] = f.x, sf[1] = f.y, sf[2] = f.z, sf[3] = f.w;
-        dur[0] = d.x, dur[1] = d.y, dur[2] = d.z, dur[3] = d.w;
-        row[0] = r.x & 0xFFFFu, row[1] = r.x >> 16, row[2] = r.y & 0xFFFFu, row[3] = r.y >> 16;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) live[j] = i0 + j >= a.begin;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const uint64_t i = i0 + j;
-          live[j] = i < hi && i >= a.begin;
-          st[j] = live[j] ? a.start[i] : 0ull;
-          sf[j] = live[j] ? a.svcfl[i] : 0u;
-          dur[j] = live[j] ? a.dur[i] : 0u;
-          row[j] = live[j] ? (uint32_t)a.rows[i] : 0u;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kLoadPairs * 2; ++j) {
-        // root / orphan codes of the aggregation that wrote the rows -> this call's
-        const uint32_t p = row[j] >= a.S0 ? row[j] - a.S0 + a.S : row[j];
-        const uint32_t svc = sf[j] & 0xFFFFu;
-        edge[j] = p < a.S + ANOMOD_ROOT_ROWS && svc < a.S ? p * a.S + svc : kNoWin;
-      }
+      uint32_t sf[4];
+      stream::load_rows(L, a.rows, a.svcfl, a.dur, a.S, a.S0, edge, dur, sf, a.start, st);
     } else {
-      unsigned long long key[kLoadPairs * 2];
-      if (b + kLoadBatch <= hi) {
-#pragma unroll
-        for (int j = 0; j < kLoadPairs; ++j) {
-          const uint64_t i = b + ((uint64_t)j * kLoadThreads + tid) * 2;
-          const u64x2 k = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.keys + i));
-          const u64x2 s = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.start + i));
-          key[2 * j] = k.x, key[2 * j + 1] = k.y;
-          st[2 * j] = s.x, st[2 * j + 1] = s.y;
-          live[2 * j] = i >= a.begin;
-          live[2 * j + 1] = i + 1 >= a.begin;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < kLoadPairs * 2; ++j) {
-          const uint64_t i = b + ((uint64_t)(j >> 1) * kLoadThreads + tid) * 2 + (j & 1);
-          live[j] = i < hi && i >= a.begin;
-          key[j] = live[j] ? a.keys[i] : 0ull;
-          st[j] = live[j] ? a.start[i] : 0ull;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < kLoadPairs * 2; ++j) {
-        edge[j] = (uint32_t)(key[j] >> 32);
-        dur[j] = (uint32_t)key[j];
-      }
+      stream::load_keys(L, a.keys, edge, dur, a.start, st);
     }
-    uint32_t wa[kLoadPairs * 2];              // window of the head partial, kNoWin: none
-    unsigned long long head[kLoadPairs * 2];  // the head partial
-    uint32_t lmin = kNoWin;
+    uint32_t wa[4];              // window of the head partial, kNone: none
+    unsigned long long head[4];  // the head partial
+    uint32_t lmin = stream::kNone;
 #pragma unroll
-    for (int j = 0; j < kLoadPairs * 2; ++j) {
-      wa[j] = kNoWin;
+    for (int j = 0; j < 4; ++j) {
+      wa[j] = stream::kNone;
       head[j] = 0ull;
-      if (!live[j]) continue;
+      if (!L.live[j]) continue;
       if (edge[j] >= E) {  // never for rows of the aggregation / keys of span_edge_keys
         ++bad;
         continue;
@@ -238,60 +162,21 @@ __global__ __launch_bounds__(kLoadThreads) void edge_load_kernel(LoadArgs a) {
       }
     }
     if (!a.busy) continue;  // (uniform) only the carried table was asked for
-    if (Wt) {               // (uniform) move the tile's anchor to the batch's smallest window
-      for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)lmin, o);
-        lmin = lmin < other ? lmin : other;
-      }
-      if ((tid & 63u) == 0 && lmin != kNoWin) atomicMin(&s_min[it % 3u], lmin);
-      __syncthreads();  // also: the previous batch's LDS atomics have landed
-      const uint32_t bmin = s_min[it % 3u];
-      if (tid == 0) s_min[(it + 2u) % 3u] = kNoWin;  // read last in batch it - 1
-      if (bmin != kNoWin) {
-        if (!anchored) {
-          anchored = true;
-          base = bmin;
-        } else if (bmin > base) {
-          const uint32_t adv = bmin - base;
-          const uint32_t nf = adv < Wt ? adv : Wt;
-          for (uint32_t k = 0; k < nf; ++k) {
-            const uint32_t s = slot0 + k;
-            flush_slot(s >= Wt ? s - Wt : s, base + k);
-          }
-          slot0 = adv < Wt ? (slot0 + adv >= Wt ? slot0 + adv - Wt : slot0 + adv) : 0u;
-          base = bmin;
-          __syncthreads();  // slots are clean before anyone reuses them
-        }
-      }
-    }
+    ring.advance(it, lmin, tid, flush_slot);
 #pragma unroll
-    for (int j = 0; j < kLoadPairs * 2; ++j) {
-      if (wa[j] == kNoWin) continue;
-      if (anchored && wa[j] >= base && wa[j] - base < Wt) {
-        uint32_t s = slot0 + (wa[j] - base);
-        s = s >= Wt ? s - Wt : s;
+    for (int j = 0; j < 4; ++j) {
+      if (wa[j] == stream::kNone) continue;
+      const uint32_t s = ring.slot_of(wa[j]);
+      if (s != stream::kNone) {
         atomicAdd(&l_busy[s * E + edge[j]], head[j]);
       } else {
         atomicAdd(a.busy + (uint64_t)wa[j] * E + edge[j], head[j]);
       }
     }
   }
-  if (Wt && a.busy) {
-    __syncthreads();
-    if (anchored)
-      for (uint32_t k = 0; k < Wt && (uint64_t)base + k < T; ++k) {
-        const uint32_t s = slot0 + k;
-        flush_slot(s >= Wt ? s - Wt : s, base + k);
-      }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    outside += (uint32_t)__shfl_xor((int)outside, o);
-    bad += (uint32_t)__shfl_xor((int)bad, o);
-  }
-  if ((tid & 63u) == 0) {
-    if (outside) atomicAdd(a.misc, (unsigned long long)outside);
-    if (bad) atomicAdd(a.misc + 1, (unsigned long long)bad);
-  }
+  if (a.busy) ring.finish(T, flush_slot);
+  stream::count_add(a.misc, outside, tid);
+  stream::count_add(a.misc + 1, bad, tid);
 }
 
 // The prefix sums along w and the full * step fold, over the T x E cells.
@@ -390,17 +275,6 @@ __global__ __launch_bounds__(kScanThreads) void edge_load_scan_kernel(ScanArgs a
   }
 }
 
-// Value of a numeric environment cap, "no cap" when unset or not a number;
-// ANOMOD_EDGE_LOAD_WGS must be at least 1.
-uint64_t load_env_cap(const char* name) {
-  const char* e = getenv(name);
-  if (!e || !*e) return 0xFFFFFFFFull;
-  char* end = nullptr;
-  const unsigned long long v = strtoull(e, &end, 10);
-  if (*end) return 0xFFFFFFFFull;
-  return !strcmp(name, "ANOMOD_EDGE_LOAD_WGS") && v == 0 ? 1 : (uint64_t)v;
-}
-
 }  // namespace
 }  // namespace anomod
 
@@ -413,25 +287,10 @@ uint32_t anomod_edge_load_scan_segment(void) { return kLoadSeg; }
 int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_edge_load* out) {
   ANOMOD_REQUIRE(nullptr, ctx && spans && out, "anomod_edge_load_spans: NULL argument");
   const uint32_t S = out->n_services, T = out->n_windows;
-  ANOMOD_REQUIRE(ctx, S >= 1 && S <= 4096, "n_services=%u out of range [1, 4096]", S);
-  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
-  ANOMOD_REQUIRE(ctx, T >= 1 && T <= 65536, "n_windows=%u outside [1, 65536]", T);
-  ANOMOD_REQUIRE(ctx, (uint64_t)T * E <= (1ull << 24), "n_windows * edge rows = %u * %u > 2^24", T,
-                 E);
-  ANOMOD_REQUIRE(ctx, out->step_us >= 1, "step_us must be at least 1");
-  ANOMOD_REQUIRE(ctx, spans->device == ctx->device, "span set lives on another device");
-  ANOMOD_REQUIRE(ctx, spans->grouped, "span set is not grouped by trace: anomod_spans_group first");
-  if (!spans->start_us) {
-    set_error(ctx, "span set has no start-time column: anomod_spans_set_start_us first");
-    return ANOMOD_ESTATE;
-  }
-  ANOMOD_REQUIRE(ctx, spans->n_spans == 0 || spans->max_svc < S,
-                 "span service index %u >= n_services %u", spans->max_svc, S);
-  uint64_t in_traces[2];
-  if (spans->n_traces && spans->n_spans)
-    if (int rc = bind(ctx)) return rc;
-  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
-  const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
+  uint32_t E = 0;
+  uint64_t in_traces[2], n = 0;
+  if (int rc = stream_table_args(ctx, S, T, out->step_us, &E)) return rc;
+  if (int rc = stream_set_args(ctx, spans, S, true, ANOMOD_EINVAL, in_traces, &n)) return rc;
   const uint64_t TE = (uint64_t)T * E;
   out->outside = 0;
   if (n == 0) {
@@ -439,54 +298,39 @@ int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_ed
     if (out->carried) memset(out->carried, 0, TE * 8);
     return ANOMOD_OK;
   }
-  // the rows form: complete parent rows over exactly the spans in traces
-  const bool rows = span_rows_ready(spans) && spans->rows_lo == in_traces[0] &&
-                    spans->rows_hi == in_traces[1];
+  EdgeSource src(spans, in_traces, n);
   const uint32_t G = (T + kLoadSeg - 1) / kLoadSeg;
   // One workspace in the windowed table's slot: (keys form: keys | the key
   // walk's words |) misc + the requested tables (zeroed together) | the scan's
   // segment totals.
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t b_keys = rows ? 0 : al(n * 8);
-  const size_t b_ws = rows ? 0 : al(span_edge_keys_ws_bytes(spans));
-  const size_t b_u64 = al(TE * 8), b_tot = G > 1 ? al((size_t)G * E * 8) : 0;
+  const size_t b_u64 = Carve::al(TE * 8), b_tot = G > 1 ? Carve::al((size_t)G * E * 8) : 0;
   const size_t b_tab = 256 + (out->busy_us ? 2 * b_u64 : 0) + (out->carried ? b_u64 : 0);
   const size_t b_scan = (out->busy_us ? b_tot : 0) + (out->carried ? b_tot : 0);
   char* w = nullptr;
-  if (int rc = ensure_scratch(ctx, kScratchEdgeWindows, b_keys + b_ws + b_tab + b_scan,
+  if (int rc = ensure_scratch(ctx, kScratchEdgeWindows, src.b_keys + src.b_ws + b_tab + b_scan,
                               reinterpret_cast<void**>(&w)))
     return rc;
+  Carve cv{w + src.b_keys + src.b_ws};
   LoadArgs a{};
-  auto* keys = reinterpret_cast<unsigned long long*>(w);
-  auto* ws = reinterpret_cast<unsigned long long*>(w + b_keys);
-  char* t = w + b_keys + b_ws;
-  a.misc = reinterpret_cast<unsigned long long*>(t);
-  t += 256;
-  auto take = [&](bool want, size_t bytes) -> unsigned long long* {
-    char* p = want ? t : nullptr;
-    if (want) t += bytes;
-    return reinterpret_cast<unsigned long long*>(p);
-  };
-  a.busy = take(out->busy_us, b_u64);
-  a.dfull = take(out->busy_us, b_u64);
-  a.dcar = take(out->carried, b_u64);
+  a.misc = cv.take<unsigned long long>(256);
+  a.busy = cv.take<unsigned long long>(b_u64, out->busy_us);
+  a.dfull = cv.take<unsigned long long>(b_u64, out->busy_us);
+  a.dcar = cv.take<unsigned long long>(b_u64, out->carried);
   ScanArgs sc{};
   sc.busy = a.busy;
   sc.dfull = a.dfull;
   sc.dcar = a.dcar;
-  sc.tf = take(out->busy_us && G > 1, b_tot);
-  sc.tc = take(out->carried && G > 1, b_tot);
+  sc.tf = cv.take<unsigned long long>(b_tot, out->busy_us && G > 1);
+  sc.tc = cv.take<unsigned long long>(b_tot, out->carried && G > 1);
   sc.step = out->step_us;
   sc.T = T;
   sc.E = E;
   sc.G = G;
-  if (rows) {
+  if (src.rows) {
     a.rows = spans->parent_row;
     a.svcfl = spans->svc_flags;
     a.dur = spans->dur_us;
     a.S0 = spans->rows_S;
-  } else {
-    a.keys = keys;
   }
   a.start = spans->start_us;
   a.begin = in_traces[0];
@@ -499,26 +343,20 @@ int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_ed
   a.Wt = out->busy_us ? std::min<uint32_t>(kLoadLdsBudget / (E * 8u), T) : 0u;
   // (tests, A/B: fewer tile windows — 0 = every partial to global atomics — and
   // fewer workgroups, so that small sets give a workgroup several batches)
-  a.Wt = std::min<uint32_t>(a.Wt, (uint32_t)load_env_cap("ANOMOD_EDGE_LOAD_TILE"));
+  a.Wt = std::min<uint32_t>(a.Wt, (uint32_t)env_cap("ANOMOD_EDGE_LOAD_TILE"));
   const size_t lds = (size_t)a.Wt * E * 8;
-  auto fn = rows ? edge_load_kernel<kSrcRows> : edge_load_kernel<kSrcKeys>;
-  int per_cu = 0;
-  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                      &per_cu, reinterpret_cast<const void*>(fn), kLoadThreads, lds));
-  // persistent workgroups, one contiguous range of whole batches each
-  const uint64_t batches = (n + kLoadBatch - 1) / kLoadBatch;
-  uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * (per_cu > 0 ? per_cu : 1), batches);
-  grid = std::min<uint64_t>(grid, load_env_cap("ANOMOD_EDGE_LOAD_WGS"));
-  a.per_wg = (batches + grid - 1) / grid * kLoadBatch;
-  if (a.per_wg > kLoadMaxRange) a.per_wg = kLoadMaxRange;  // (more workgroups than are resident)
-  grid = (n + a.per_wg - 1) / a.per_wg;
-  if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests, timing)
+  auto fn = src.rows ? edge_load_kernel<kSrcRows> : edge_load_kernel<kSrcKeys>;
+  uint64_t grid = 0;
+  if (int rc = stream_geometry(ctx, fn, kLoadThreads, lds, n, "ANOMOD_EDGE_LOAD_WGS", &a.per_wg,
+                               &grid))
+    return rc;
+  if (log_kernel())  // (tests, timing)
     fprintf(stderr, "anomod: edge load kernel edge_load_kernel<%s>, tile %u windows\n",
-            rows ? "rows" : "keys", a.Wt);
+            src.rows ? "rows" : "keys", a.Wt);
   if (int rc = stage_begin(ctx, kStageEdgeLoad)) return rc;
   ANOMOD_HIP(ctx, hipMemsetAsync(a.misc, 0, b_tab, ctx->stream));
-  if (!rows)
-    if (int rc = span_edge_keys(ctx, spans, S, keys, ws)) return rc;
+  if (int rc = src.fill(ctx, spans, S, w)) return rc;
+  a.keys = src.keys;
   if (int rc = stage_begin(ctx, kStageEdgeLoadKernel)) return rc;
   hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kLoadThreads), lds, ctx->stream, a);
   ANOMOD_HIP(ctx, hipGetLastError());
@@ -537,19 +375,10 @@ int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_ed
   ANOMOD_HIP(ctx, hipGetLastError());
   if (int rc = stage_end(ctx, kStageEdgeLoadScan)) return rc;
   if (int rc = stage_end(ctx, kStageEdgeLoad)) return rc;
-  unsigned long long misc[2] = {0ull, 0ull};
-  ANOMOD_HIP(ctx, hipMemcpyAsync(misc, a.misc, 16, hipMemcpyDeviceToHost, ctx->stream));
-  if (out->busy_us)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->busy_us, a.busy, TE * 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-  if (out->carried)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->carried, a.dcar, TE * 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-  ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (misc[1]) {
-    set_error(ctx, "edge load: %llu spans carry no edge row (internal error)", misc[1]);
-    return ANOMOD_ESTATE;
-  }
+  ANOMOD_HIP(ctx, stream_back(ctx, out->busy_us, a.busy, TE * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->carried, a.dcar, TE * 8));
+  unsigned long long misc[2];
+  if (int rc = stream_finish(ctx, a.misc, 1, "edge load", "row", misc)) return rc;
   out->outside = misc[0];
   return ANOMOD_OK;
 }

@@ -8,9 +8,8 @@
 // span's row is by construction the one anomod_edge_aggregate_spans counts it
 // in.  window_cell_keys_kernel then widens the key in place to
 // cell << 32 | dur_us with cell = w * E + row and w the window rule of
-// edge_windows_kernel (start < t0 first, then (start - t0) / step against T):
-// a stream over span positions, 16 B read (key 8, start 8) and 8 B written
-// per span.  A span in no cell — outside [0, T), before trace_ptr[0], or with
+// edge_windows_kernel (window_of, edge_stream.h): the keys form of the shared
+// edge stream, 16 B read (key 8, start 8) and 8 B written per span.  A span in no cell — outside [0, T), before trace_ptr[0], or with
 // a key that names no row — takes the sentinel cell T * E, which sorts behind
 // every real cell.  One radix sort (radix.hip) over bits [0, 32 + bits(T * E))
 // orders the spans by (cell, latency); window_cell_bounds_kernel streams the
@@ -18,27 +17,22 @@
 // window_pick_kernel reads the picks.  Every value is an integer: results are
 // bit-exact for any launch geometry.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
-#include "common.h"
+#include "edge_stream.h"
 #include "radix.h"
-#include "walk.h"
 
 namespace anomod {
 namespace {
 
 constexpr int kCellThreads = 256;
-constexpr int kCellPairs = 2;                              // 16-B (two-span) loads per lane per batch
-constexpr int kCellBatch = kCellThreads * kCellPairs * 2;  // spans per workgroup iteration
 constexpr uint32_t kMaxQ = 8;
-
-using u64x2 = unsigned long long __attribute__((ext_vector_type(2)));
+using CellLanes = stream::Lanes<kCellThreads, 2>;  // 1024 spans per workgroup iteration
 
 struct CellArgs {
   unsigned long long* keys;  // [n] in: edge << 32 | dur; out: cell << 32 | dur
   const uint64_t* start;     // [n]
-  uint64_t begin, n, per_wg; // spans [begin, n) lie in traces; per_wg: a multiple of kCellBatch
+  uint64_t begin, n, per_wg; // spans [begin, n) lie in traces; per_wg: a multiple of the batch
   uint64_t t0, step;
   uint32_t T, E, TE;
   unsigned long long* misc;  // [0] outside, [1] spans whose key names no edge row
@@ -47,61 +41,34 @@ struct CellArgs {
 // (no __restrict__: keys is read and written, each position by one lane)
 __global__ __launch_bounds__(kCellThreads) void window_cell_keys_kernel(CellArgs a) {
   const uint32_t tid = threadIdx.x;
-  const uint64_t lo = (uint64_t)blockIdx.x * a.per_wg;
-  const uint64_t hi = lo + a.per_wg < a.n ? lo + a.per_wg : a.n;
+  uint64_t lo, hi;
+  stream::wg_range(a.per_wg, a.n, &lo, &hi);
   const unsigned long long none = (unsigned long long)a.TE << 32;
   uint32_t outside = 0, bad = 0;
-  auto widen = [&](unsigned long long key, uint64_t st, bool live) -> unsigned long long {
-    const uint32_t dur = (uint32_t)key;
-    if (!live) return none;
-    if ((uint32_t)(key >> 32) >= a.E) {  // never for keys of span_edge_keys
-      ++bad;
-      return none | dur;
-    }
-    // start < t0 first (unsigned), then w against T: t0 + T * step may pass 2^64
-    const uint64_t w = st >= a.t0 ? (st - a.t0) / a.step : (uint64_t)a.T;
-    if (w >= (uint64_t)a.T) {
-      ++outside;
-      return none | dur;
-    }
-    const uint32_t cell = (uint32_t)w * a.E + (uint32_t)(key >> 32);
-    return (unsigned long long)cell << 32 | dur;
-  };
-  for (uint64_t b = lo; b < hi; b += kCellBatch) {
-    if (b + kCellBatch <= hi) {  // (b is a multiple of kCellBatch: 16-B aligned pairs)
-      u64x2 k[kCellPairs], s[kCellPairs];
+  for (uint64_t b = lo; b < hi; b += CellLanes::kBatch) {
+    CellLanes L(b, hi, a.begin, tid);
+    unsigned long long key[4];
+    uint64_t st[4];
+    L.load(a.keys, key, a.start, st);
 #pragma unroll
-      for (int j = 0; j < kCellPairs; ++j) {
-        const uint64_t i = b + ((uint64_t)j * kCellThreads + tid) * 2;
-        k[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.keys + i));
-        s[j] = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.start + i));
-      }
-#pragma unroll
-      for (int j = 0; j < kCellPairs; ++j) {
-        const uint64_t i = b + ((uint64_t)j * kCellThreads + tid) * 2;
-        u64x2 o;
-        o.x = widen(k[j].x, s[j].x, i >= a.begin);
-        o.y = widen(k[j].y, s[j].y, i + 1 >= a.begin);
-        *reinterpret_cast<u64x2*>(a.keys + i) = o;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < kCellPairs * 2; ++j) {
-        const uint64_t i = b + ((uint64_t)(j >> 1) * kCellThreads + tid) * 2 + (j & 1);
-        if (i >= hi) continue;
-        const bool live = i >= a.begin;
-        a.keys[i] = widen(live ? a.keys[i] : 0ull, live ? a.start[i] : 0ull, live);
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t row = (uint32_t)(key[j] >> 32), dur = (uint32_t)key[j];
+      key[j] = none;
+      if (!L.live[j]) continue;
+      key[j] |= dur;
+      if (row >= a.E) {  // never for keys of span_edge_keys
+        ++bad;
+      } else if (const uint32_t w = stream::window_of(st[j], a.t0, a.step, a.T);
+                 w == stream::kNone) {
+        ++outside;
+      } else {
+        key[j] = (unsigned long long)(w * a.E + row) << 32 | dur;
       }
     }
+    L.store(a.keys, key);
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    outside += (uint32_t)__shfl_xor((int)outside, o);
-    bad += (uint32_t)__shfl_xor((int)bad, o);
-  }
-  if ((tid & 63u) == 0) {
-    if (outside) atomicAdd(a.misc, (unsigned long long)outside);
-    if (bad) atomicAdd(a.misc + 1, (unsigned long long)bad);
-  }
+  stream::count_add(a.misc, outside, tid);
+  stream::count_add(a.misc + 1, bad, tid);
 }
 
 // Where each cell's run of the sorted keys begins and ends.  Position i opens
@@ -111,7 +78,7 @@ __global__ __launch_bounds__(kCellThreads) void window_cell_keys_kernel(CellArgs
 // no entry.  m <= 2^32 - 4097: positions are u32.
 struct BoundArgs {
   const unsigned long long* sk;  // [m] sorted cell << 32 | dur
-  uint64_t m, per_wg;            // per_wg: a multiple of kCellBatch
+  uint64_t m, per_wg;            // per_wg: a multiple of the batch
   uint32_t TE;
   uint32_t* cbegin;              // [TE]
   uint32_t* cend;                // [TE]
@@ -128,15 +95,17 @@ __device__ inline void cell_edge(const BoundArgs& a, uint64_t i, uint32_t cur, u
 
 __global__ __launch_bounds__(kCellThreads) void window_cell_bounds_kernel(BoundArgs a) {
   const uint32_t tid = threadIdx.x;
-  const uint64_t lo = (uint64_t)blockIdx.x * a.per_wg;
-  const uint64_t hi = lo + a.per_wg < a.m ? lo + a.per_wg : a.m;
-  for (uint64_t b = lo; b < hi; b += kCellBatch) {
-    if (b + kCellBatch <= hi) {  // (b is a multiple of kCellBatch: 16-B aligned pairs)
+  uint64_t lo, hi;
+  stream::wg_range(a.per_wg, a.m, &lo, &hi);
+  for (uint64_t b = lo; b < hi; b += CellLanes::kBatch) {
+    CellLanes L(b, hi, 0, tid);
+    unsigned long long k[4];
+    L.load(a.sk, k);
+    if (L.full) {
 #pragma unroll
-      for (int j = 0; j < kCellPairs; ++j) {
-        const uint64_t i = b + ((uint64_t)j * kCellThreads + tid) * 2;
-        const u64x2 k = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.sk + i));
-        const uint32_t c0 = (uint32_t)(k.x >> 32), c1 = (uint32_t)(k.y >> 32);
+      for (int j = 0; j < 4; j += 2) {
+        const uint64_t i = L.pos(j);
+        const uint32_t c0 = (uint32_t)(k[j] >> 32), c1 = (uint32_t)(k[j + 1] >> 32);
         // the cell of position i - 1: the lane below holds it, except at a
         // wave's first lane (the wave, workgroup or range before this one)
         uint32_t prev = (uint32_t)__shfl_up((int)c1, 1);
@@ -146,12 +115,11 @@ __global__ __launch_bounds__(kCellThreads) void window_cell_bounds_kernel(BoundA
       }
     } else {
 #pragma unroll
-      for (int j = 0; j < kCellPairs * 2; ++j) {
-        const uint64_t i = b + ((uint64_t)(j >> 1) * kCellThreads + tid) * 2 + (j & 1);
-        if (i >= hi) continue;
-        const uint32_t cur = (uint32_t)(a.sk[i] >> 32);
+      for (int j = 0; j < 4; ++j) {
+        const uint64_t i = L.pos(j);
+        if (!L.live[j]) continue;
         const uint32_t prev = i > 0 ? (uint32_t)(a.sk[i - 1] >> 32) : 0u;
-        cell_edge(a, i, cur, prev, i == 0);
+        cell_edge(a, i, (uint32_t)(k[j] >> 32), prev, i == 0);
       }
     }
   }
@@ -184,25 +152,12 @@ __global__ __launch_bounds__(256) void window_pick_kernel(PickArgs a) {
   a.q_us[t] = c ? (uint32_t)a.sk[(uint64_t)b + (uint64_t)((double)c * ((double)q / 100.0))] : 0u;
 }
 
-// Workgroup cap of the two stream kernels (tests: one workgroup over the whole
-// set, many small ones); "no cap" when unset or not a number, at least 1.
-uint64_t wgs_cap() {
-  const char* e = getenv("ANOMOD_EDGE_WINDOW_QUANTILES_WGS");
-  if (!e || !*e) return 0xFFFFFFFFull;
-  char* end = nullptr;
-  const unsigned long long v = strtoull(e, &end, 10);
-  if (*end) return 0xFFFFFFFFull;
-  return v == 0 ? 1 : (uint64_t)v;
-}
-
-// Persistent workgroups over n positions, one contiguous range of whole
-// batches each: *per_wg spans a workgroup, the grid as the return value.
-uint64_t stream_grid(const anomod_ctx* ctx, uint64_t n, uint64_t* per_wg) {
-  const uint64_t batches = (n + kCellBatch - 1) / kCellBatch;
-  uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * 8, batches);
-  grid = std::min<uint64_t>(grid, wgs_cap());
-  *per_wg = (batches + grid - 1) / grid * kCellBatch;
-  return (n + *per_wg - 1) / *per_wg;
+// Geometry of the two stream kernels: eight workgroups a CU, capped by
+// ANOMOD_EDGE_WINDOW_QUANTILES_WGS (tests: one workgroup over the whole set,
+// many small ones), no range clamp (positions are u64 throughout).
+uint64_t cell_grid(const anomod_ctx* ctx, uint64_t n, uint64_t* per_wg) {
+  return stream_grid(ctx, n, CellLanes::kBatch, 8, env_cap("ANOMOD_EDGE_WINDOW_QUANTILES_WGS", 1),
+                     ~0ull, per_wg);
 }
 
 }  // namespace
@@ -217,33 +172,14 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   ANOMOD_REQUIRE(nullptr, ctx && spans && out,
                  "anomod_edge_window_quantiles_spans: NULL argument");
   const uint32_t S = out->n_services, T = out->n_windows, nq = out->nq;
-  ANOMOD_REQUIRE(ctx, S >= 1 && S <= 4096, "n_services=%u out of range [1, 4096]", S);
-  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
-  ANOMOD_REQUIRE(ctx, T >= 1 && T <= 65536, "n_windows=%u outside [1, 65536]", T);
-  ANOMOD_REQUIRE(ctx, (uint64_t)T * E <= (1ull << 24), "n_windows * edge rows = %u * %u > 2^24", T,
-                 E);
-  ANOMOD_REQUIRE(ctx, out->step_us >= 1, "step_us must be at least 1");
+  uint32_t E = 0;
+  if (int rc = stream_table_args(ctx, S, T, out->step_us, &E)) return rc;
   ANOMOD_REQUIRE(ctx, nq >= 1 && nq <= kMaxQ, "nq=%u outside [1, %u]", nq, kMaxQ);
   ANOMOD_REQUIRE(ctx, out->q_pct && out->q_us, "anomod_edge_window_quantiles: NULL q_pct or q_us");
   for (uint32_t k = 0; k < nq; ++k)
     ANOMOD_REQUIRE(ctx, out->q_pct[k] <= 99, "q_pct[%u]=%u outside [0, 99]", k, out->q_pct[k]);
-  ANOMOD_REQUIRE(ctx, spans->device == ctx->device, "span set lives on another device");
-  if (!spans->grouped) {
-    set_error(ctx, "span set is not grouped by trace: anomod_spans_group first");
-    return ANOMOD_ESTATE;
-  }
-  if (!spans->start_us) {
-    set_error(ctx, "span set has no start-time column: anomod_spans_set_start_us first");
-    return ANOMOD_ESTATE;
-  }
-  ANOMOD_REQUIRE(ctx, spans->n_spans == 0 || spans->max_svc < S,
-                 "span service index %u >= n_services %u", spans->max_svc, S);
-  // the spans that lie in traces
-  uint64_t in_traces[2];
-  if (spans->n_traces && spans->n_spans)
-    if (int rc = bind(ctx)) return rc;
-  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
-  const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
+  uint64_t in_traces[2], n = 0;
+  if (int rc = stream_set_args(ctx, spans, S, true, ANOMOD_ESTATE, in_traces, &n)) return rc;
   const uint64_t m = n ? n - in_traces[0] : 0;  // the spans that are sorted
   // one radix sort over the in-trace spans' keys (u32 tile offsets inside)
   ANOMOD_REQUIRE(ctx, m <= kMaxSortKeys,
@@ -294,7 +230,7 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   a.E = E;
   a.TE = TE;
   a.misc = misc_d;
-  uint64_t grid = stream_grid(ctx, n, &a.per_wg);
+  uint64_t grid = cell_grid(ctx, n, &a.per_wg);
   hipLaunchKernelGGL(window_cell_keys_kernel, dim3((unsigned)grid), dim3(kCellThreads), 0,
                      ctx->stream, a);
   ANOMOD_HIP(ctx, hipGetLastError());
@@ -303,7 +239,7 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   ANOMOD_HIP(ctx, radix_sort_u64(reinterpret_cast<const uint64_t*>(keys + in_traces[0]),
                                  reinterpret_cast<uint64_t*>(sorted), m, 0, 32 + cbits, tmp,
                                  sort_tmp, ctx->stream, &passes));
-  if (const char* lg = getenv("ANOMOD_LOG_KERNEL"); lg && lg[0] == '1')  // (tests, timing)
+  if (log_kernel())  // (tests, timing)
     fprintf(stderr, "anomod: edge window quantiles: %llu keys of %d bits, %d sort passes\n",
             (unsigned long long)m, 32 + cbits, passes);
 
@@ -313,7 +249,7 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   ba.TE = TE;
   ba.cbegin = cbegin;
   ba.cend = cend;
-  grid = stream_grid(ctx, m, &ba.per_wg);
+  grid = cell_grid(ctx, m, &ba.per_wg);
   hipLaunchKernelGGL(window_cell_bounds_kernel, dim3((unsigned)grid), dim3(kCellThreads), 0,
                      ctx->stream, ba);
   ANOMOD_HIP(ctx, hipGetLastError());
@@ -332,17 +268,10 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
                      ctx->stream, pa);
   ANOMOD_HIP(ctx, hipGetLastError());
 
-  unsigned long long misc[2] = {0ull, 0ull};
-  ANOMOD_HIP(ctx, hipMemcpyAsync(misc, misc_d, 16, hipMemcpyDeviceToHost, ctx->stream));
-  if (out->count)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->count, d_cnt, (size_t)TE * 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-  ANOMOD_HIP(ctx, hipMemcpyAsync(out->q_us, d_q, picks * 4, hipMemcpyDeviceToHost, ctx->stream));
-  ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (misc[1]) {
-    set_error(ctx, "edge window quantiles: %llu spans carry no edge key (internal error)", misc[1]);
-    return ANOMOD_ESTATE;
-  }
+  ANOMOD_HIP(ctx, stream_back(ctx, out->count, d_cnt, (size_t)TE * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->q_us, d_q, picks * 4));
+  unsigned long long misc[2];
+  if (int rc = stream_finish(ctx, misc_d, 1, "edge window quantiles", "key", misc)) return rc;
   out->outside = misc[0];
   return ANOMOD_OK;
 }

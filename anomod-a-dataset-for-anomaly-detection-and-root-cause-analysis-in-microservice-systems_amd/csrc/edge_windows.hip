@@ -5,49 +5,36 @@
 // Two passes.  Pass 1 is the aggregation kernels' own walk in its key form
 // (span_edge_keys, edge_agg.hip): keys[i] = edge row << 32 | dur_us by span
 // position, so the edge of a span is by construction the row
-// anomod_edge_aggregate_spans counts it in.  Pass 2 (edge_windows_kernel) is a
-// plain stream over span positions: 20 B read per span (key 8, start 8,
-// svc|flags 4), accumulated into cell w * E + edge.  The 16 B / span key round
-// trip through HBM is the known cost of not fusing the accumulation into the
-// walk.
+// anomod_edge_aggregate_spans counts it in.  Pass 2 (edge_windows_kernel) is
+// the keys form of the shared edge stream (edge_stream.h): 20 B read per span
+// (key 8, start 8, svc|flags 4), accumulated into cell w * E + edge.  The 16 B
+// / span key round trip through HBM is the known cost of not fusing the
+// accumulation into the walk.
 //
-// Pass 2 privatises cells in LDS as a sliding tile of Wt consecutive windows:
-// every workgroup owns one contiguous span range, and collector files (and the
+// Pass 2 privatises cells in LDS in the stream's sliding window ring: every
+// workgroup owns one contiguous span range, and collector files (and the
 // synthetic fill) are close to time-ordered, so a range touches a narrow band
-// of windows.  The tile is a ring of Wt window slots x E cells (count | errors
-// << 32 as one u64, sum u64, max u32 = 20 B a cell) anchored at the smallest
-// window of the current batch; when the stream moves past a window its slot is
-// flushed to the global table with integer atomics.  A span whose window falls
-// outside the tile goes straight to global atomics, so correctness never
-// depends on the hit rate; Wt = 0 (a table too wide for one window slot) is
-// the all-global kernel.  A workgroup's range holds < 2^32 spans, so the u32
+// of windows.  A cell is count | errors << 32 as one u64, sum u64, max u32 =
+// 20 B, in three planes.  A workgroup's range holds < 2^32 spans, so the u32
 // halves of the packed count | errors word cannot carry into each other.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
-#include "common.h"
-#include "walk.h"
+#include "edge_stream.h"
 
 namespace anomod {
 namespace {
 
 constexpr int kWinThreads = 512;
-constexpr int kWinPairs = 2;                            // 16-B (two-span) loads per lane per batch
-constexpr int kWinBatch = kWinThreads * kWinPairs * 2;  // spans per workgroup iteration
-constexpr uint32_t kWinLdsBudget = 64u * 1024u - 64u;   // two workgroups per CU (+ s_min)
+constexpr uint32_t kWinLdsBudget = 64u * 1024u - 64u;  // two workgroups per CU (+ the ring's minima)
 constexpr uint32_t kCellBytes = 20;
-constexpr uint64_t kMaxRange = 1ull << 31;              // spans per workgroup (u32 LDS counts)
-constexpr uint32_t kNoWindow = 0xFFFFFFFFu;
-
-using u64x2 = unsigned long long __attribute__((ext_vector_type(2)));
-using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
+using WinLanes = stream::Lanes<kWinThreads, 2>;  // 2048 spans per workgroup iteration
 
 struct WinArgs {
   const unsigned long long* keys;   // [n] edge << 32 | dur
   const uint64_t* start;            // [n]
   const uint32_t* svcfl;            // [n] svc | flags << 16
-  uint64_t begin, n, per_wg;        // spans [begin, n) lie in traces; per_wg: a multiple of kWinBatch
+  uint64_t begin, n, per_wg;        // spans [begin, n) lie in traces; per_wg: a multiple of the batch
   uint64_t t0, step;
   uint32_t T, E, Wt;
   unsigned long long* count;        // [T * E] each, or NULL
@@ -68,22 +55,21 @@ __device__ inline void cell_global(const WinArgs& a, uint64_t cell, uint32_t cnt
 extern __shared__ __align__(16) unsigned char win_lds[];
 
 __global__ __launch_bounds__(kWinThreads) void edge_windows_kernel(WinArgs a) {
-  const uint32_t E = a.E, Wt = a.Wt;
-  const uint32_t cells = Wt * E;
+  const uint32_t E = a.E;
+  const uint32_t cells = a.Wt * E;
   auto* l_ce = reinterpret_cast<unsigned long long*>(win_lds);  // count | errors << 32
   auto* l_sum = l_ce + cells;
   auto* l_mx = reinterpret_cast<unsigned int*>(l_sum + cells);
-  __shared__ uint32_t s_min[3];
   const uint32_t tid = threadIdx.x;
+  stream::WindowRing ring{a.Wt};
   for (uint32_t c = tid; c < cells; c += kWinThreads) {
     l_ce[c] = 0ull;
     l_sum[c] = 0ull;
     l_mx[c] = 0u;
   }
-  if (tid < 3) s_min[tid] = kNoWindow;
+  ring.init(tid);
   __syncthreads();
 
-  // window `w` of the tile [base, base + Wt) lives in slot (slot0 + w - base) mod Wt
   auto flush_slot = [&](uint32_t slot, uint32_t w) {
     for (uint32_t e = tid; e < E; e += kWinThreads) {
       const uint32_t c = slot * E + e;
@@ -96,120 +82,53 @@ __global__ __launch_bounds__(kWinThreads) void edge_windows_kernel(WinArgs a) {
     }
   };
 
-  const uint64_t lo = (uint64_t)blockIdx.x * a.per_wg;
-  const uint64_t hi = lo + a.per_wg < a.n ? lo + a.per_wg : a.n;
-  bool anchored = false;
-  uint32_t base = 0, slot0 = 0;
+  uint64_t lo, hi;
+  stream::wg_range(a.per_wg, a.n, &lo, &hi);
   uint32_t outside = 0, bad = 0;
   uint32_t it = 0;
-  for (uint64_t b = lo; b < hi; b += kWinBatch, ++it) {
-    unsigned long long key[kWinPairs * 2];
-    uint64_t st[kWinPairs * 2];
-    uint32_t sf[kWinPairs * 2];
-    bool live[kWinPairs * 2];
-    if (b + kWinBatch <= hi) {  // (b is a multiple of kWinBatch: 16-B aligned pairs)
+  for (uint64_t b = lo; b < hi; b += WinLanes::kBatch, ++it) {
+    WinLanes L(b, hi, a.begin, tid);
+    uint32_t edge[4], dur[4], sf[4];
+    uint64_t st[4];
+    stream::load_keys(L, a.keys, edge, dur, a.start, st, a.svcfl, sf);
+    uint32_t w[4];
+    uint32_t lmin = stream::kNone;
 #pragma unroll
-      for (int j = 0; j < kWinPairs; ++j) {
-        const uint64_t i = b + ((uint64_t)j * kWinThreads + tid) * 2;
-        const u64x2 k = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.keys + i));
-        const u64x2 s = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(a.start + i));
-        const u32x2 f = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.svcfl + i));
-        key[2 * j] = k.x, key[2 * j + 1] = k.y;
-        st[2 * j] = s.x, st[2 * j + 1] = s.y;
-        sf[2 * j] = f.x, sf[2 * j + 1] = f.y;
-        live[2 * j] = i >= a.begin;
-        live[2 * j + 1] = i + 1 >= a.begin;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < kWinPairs * 2; ++j) {
-        const uint64_t i = b + ((uint64_t)(j >> 1) * kWinThreads + tid) * 2 + (j & 1);
-        live[j] = i < hi && i >= a.begin;
-        key[j] = live[j] ? a.keys[i] : 0ull;
-        st[j] = live[j] ? a.start[i] : 0ull;
-        sf[j] = live[j] ? a.svcfl[i] : 0u;
-      }
-    }
-    uint32_t w[kWinPairs * 2];
-    uint32_t lmin = kNoWindow;
-#pragma unroll
-    for (int j = 0; j < kWinPairs * 2; ++j) {
-      w[j] = kNoWindow;
-      if (!live[j]) continue;
-      if ((uint32_t)(key[j] >> 32) >= E) {  // never for keys of span_edge_keys
+    for (int j = 0; j < 4; ++j) {
+      w[j] = stream::kNone;
+      if (!L.live[j]) continue;
+      if (edge[j] >= E) {  // never for keys of span_edge_keys
         ++bad;
         continue;
       }
-      // start < t0 first (unsigned), then w against T: t0 + T * step may pass 2^64
-      const uint64_t q = st[j] >= a.t0 ? (st[j] - a.t0) / a.step : (uint64_t)a.T;
-      if (q >= (uint64_t)a.T) {
+      w[j] = stream::window_of(st[j], a.t0, a.step, a.T);
+      if (w[j] == stream::kNone) {
         ++outside;
         continue;
       }
-      w[j] = (uint32_t)q;
       lmin = lmin < w[j] ? lmin : w[j];
     }
-    if (Wt) {  // (uniform) move the tile's anchor to the batch's smallest window
-      for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)lmin, o);
-        lmin = lmin < other ? lmin : other;
-      }
-      if ((tid & 63u) == 0 && lmin != kNoWindow) atomicMin(&s_min[it % 3u], lmin);
-      __syncthreads();  // also: the previous batch's LDS atomics have landed
-      const uint32_t bmin = s_min[it % 3u];
-      if (tid == 0) s_min[(it + 2u) % 3u] = kNoWindow;  // read last in batch it - 1
-      if (bmin != kNoWindow) {
-        if (!anchored) {
-          anchored = true;
-          base = bmin;
-        } else if (bmin > base) {
-          const uint32_t adv = bmin - base;
-          const uint32_t nf = adv < Wt ? adv : Wt;
-          for (uint32_t k = 0; k < nf; ++k) {
-            const uint32_t s = slot0 + k;
-            flush_slot(s >= Wt ? s - Wt : s, base + k);
-          }
-          slot0 = adv < Wt ? (slot0 + adv >= Wt ? slot0 + adv - Wt : slot0 + adv) : 0u;
-          base = bmin;
-          __syncthreads();  // slots are clean before anyone reuses them
-        }
-      }
-    }
+    ring.advance(it, lmin, tid, flush_slot);
 #pragma unroll
-    for (int j = 0; j < kWinPairs * 2; ++j) {
-      if (w[j] == kNoWindow) continue;
-      const uint32_t edge = (uint32_t)(key[j] >> 32), dur = (uint32_t)key[j];
+    for (int j = 0; j < 4; ++j) {
+      if (w[j] == stream::kNone) continue;
       const uint32_t err = (sf[j] >> 16) & ANOMOD_FLAG_ERROR;
-      if (anchored && w[j] >= base && w[j] - base < Wt) {
-        uint32_t s = slot0 + (w[j] - base);
-        s = s >= Wt ? s - Wt : s;
-        const uint32_t c = s * E + edge;
+      const uint32_t s = ring.slot_of(w[j]);
+      if (s != stream::kNone) {
+        const uint32_t c = s * E + edge[j];
         atomicAdd(&l_ce[c], 1ull | ((unsigned long long)err << 32));
-        if (dur) {
-          atomicAdd(&l_sum[c], (unsigned long long)dur);
-          atomicMax(&l_mx[c], dur);
+        if (dur[j]) {
+          atomicAdd(&l_sum[c], (unsigned long long)dur[j]);
+          atomicMax(&l_mx[c], dur[j]);
         }
       } else {
-        cell_global(a, (uint64_t)w[j] * E + edge, 1u, err, dur, dur);
+        cell_global(a, (uint64_t)w[j] * E + edge[j], 1u, err, dur[j], dur[j]);
       }
     }
   }
-  if (Wt) {
-    __syncthreads();
-    if (anchored)
-      for (uint32_t k = 0; k < Wt && (uint64_t)base + k < a.T; ++k) {
-        const uint32_t s = slot0 + k;
-        flush_slot(s >= Wt ? s - Wt : s, base + k);
-      }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    outside += (uint32_t)__shfl_xor((int)outside, o);
-    bad += (uint32_t)__shfl_xor((int)bad, o);
-  }
-  if ((tid & 63u) == 0) {
-    if (outside) atomicAdd(a.misc, (unsigned long long)outside);
-    if (bad) atomicAdd(a.misc + 1, (unsigned long long)bad);
-  }
+  ring.finish(a.T, flush_slot);
+  stream::count_add(a.misc, outside, tid);
+  stream::count_add(a.misc + 1, bad, tid);
 }
 
 // start[i] = t0 + (t * period) / n_traces + pos * gap.  One wave per 64
@@ -240,17 +159,6 @@ __global__ __launch_bounds__(256) void fill_start_kernel(const uint64_t* __restr
       if (i < last) start[i] = t0 + ((g * 64 + l) * period) / n_traces + (i - pl) * gap;
     }
   }
-}
-
-// Value of a numeric environment cap, "no cap" when unset or not a number;
-// ANOMOD_EDGE_WINDOWS_WGS must be at least 1.
-uint64_t env_cap(const char* name) {
-  const char* e = getenv(name);
-  if (!e || !*e) return 0xFFFFFFFFull;
-  char* end = nullptr;
-  const unsigned long long v = strtoull(e, &end, 10);
-  if (*end) return 0xFFFFFFFFull;
-  return !strcmp(name, "ANOMOD_EDGE_WINDOWS_WGS") && v == 0 ? 1 : (uint64_t)v;
 }
 
 int ensure_start(anomod_ctx* ctx, anomod_spans* s) {
@@ -336,27 +244,10 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               anomod_edge_windows* out) {
   ANOMOD_REQUIRE(nullptr, ctx && spans && out, "anomod_edge_windows_spans: NULL argument");
   const uint32_t S = out->n_services, T = out->n_windows;
-  ANOMOD_REQUIRE(ctx, S >= 1 && S <= 4096, "n_services=%u out of range [1, 4096]", S);
-  const uint32_t E = (S + ANOMOD_ROOT_ROWS) * S;
-  ANOMOD_REQUIRE(ctx, T >= 1 && T <= 65536, "n_windows=%u outside [1, 65536]", T);
-  ANOMOD_REQUIRE(ctx, (uint64_t)T * E <= (1ull << 24), "n_windows * edge rows = %u * %u > 2^24", T,
-                 E);
-  ANOMOD_REQUIRE(ctx, out->step_us >= 1, "step_us must be at least 1");
-  ANOMOD_REQUIRE(ctx, spans->device == ctx->device, "span set lives on another device");
-  ANOMOD_REQUIRE(ctx, spans->grouped, "span set is not grouped by trace: anomod_spans_group first");
-  if (!spans->start_us) {
-    set_error(ctx, "span set has no start-time column: anomod_spans_set_start_us first");
-    return ANOMOD_ESTATE;
-  }
-  ANOMOD_REQUIRE(ctx, spans->n_spans == 0 || spans->max_svc < S,
-                 "span service index %u >= n_services %u", spans->max_svc, S);
-  // the spans that lie in traces (an upload may leave spans outside every
-  // trace: the aggregation counts none of them)
-  uint64_t in_traces[2];
-  if (spans->n_traces && spans->n_spans)
-    if (int rc = bind(ctx)) return rc;
-  if (int rc = trace_span_range(ctx, spans, in_traces)) return rc;
-  const uint64_t n = in_traces[1] > in_traces[0] ? in_traces[1] : 0;
+  uint32_t E = 0;
+  uint64_t in_traces[2], n = 0;
+  if (int rc = stream_table_args(ctx, S, T, out->step_us, &E)) return rc;
+  if (int rc = stream_set_args(ctx, spans, S, true, ANOMOD_EINVAL, in_traces, &n)) return rc;
   const uint64_t TE = (uint64_t)T * E;
   out->outside = 0;
   if (n == 0) {
@@ -368,30 +259,24 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
   }
   // One workspace: keys | the key walk's words | misc + the requested tables
   // (zeroed together).  The ctx's slot: reused by the next call, not freed.
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t b_keys = al(n * 8), b_ws = al(span_edge_keys_ws_bytes(spans));
-  const size_t b_u64 = al(TE * 8), b_u32 = al(TE * 4);
+  const size_t b_keys = Carve::al(n * 8), b_ws = Carve::al(span_edge_keys_ws_bytes(spans));
+  const size_t b_u64 = Carve::al(TE * 8), b_u32 = Carve::al(TE * 4);
   const size_t b_tab = 256 + (out->count ? b_u64 : 0) + (out->errors ? b_u64 : 0) +
                        (out->sum_us ? b_u64 : 0) + (out->max_us ? b_u32 : 0);
   char* w = nullptr;
   if (int rc = ensure_scratch(ctx, kScratchEdgeWindows, b_keys + b_ws + b_tab,
                               reinterpret_cast<void**>(&w)))
     return rc;
+  Carve cv{w};
+  auto* keys = cv.take<unsigned long long>(b_keys);
+  auto* ws = cv.take<unsigned long long>(b_ws);
   WinArgs a{};
-  a.keys = reinterpret_cast<unsigned long long*>(w);
-  auto* ws = reinterpret_cast<unsigned long long*>(w + b_keys);
-  char* t = w + b_keys + b_ws;
-  a.misc = reinterpret_cast<unsigned long long*>(t);
-  t += 256;
-  auto take = [&](bool want, size_t bytes) -> char* {
-    char* p = want ? t : nullptr;
-    if (want) t += bytes;
-    return p;
-  };
-  a.count = reinterpret_cast<unsigned long long*>(take(out->count, b_u64));
-  a.errors = reinterpret_cast<unsigned long long*>(take(out->errors, b_u64));
-  a.sum = reinterpret_cast<unsigned long long*>(take(out->sum_us, b_u64));
-  a.mx = reinterpret_cast<unsigned int*>(take(out->max_us, b_u32));
+  a.keys = keys;
+  a.misc = cv.take<unsigned long long>(256);
+  a.count = cv.take<unsigned long long>(b_u64, out->count);
+  a.errors = cv.take<unsigned long long>(b_u64, out->errors);
+  a.sum = cv.take<unsigned long long>(b_u64, out->sum_us);
+  a.mx = cv.take<unsigned int>(b_u32, out->max_us);
   a.start = spans->start_us;
   a.svcfl = spans->svc_flags;
   a.begin = in_traces[0];
@@ -405,43 +290,25 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
   // fewer workgroups, so that small sets give a workgroup several batches)
   a.Wt = std::min<uint32_t>(a.Wt, (uint32_t)env_cap("ANOMOD_EDGE_WINDOWS_TILE"));
   const size_t lds = (size_t)a.Wt * E * kCellBytes;
-  int per_cu = 0;
-  ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                      &per_cu, reinterpret_cast<const void*>(edge_windows_kernel), kWinThreads,
-                      lds));
-  // persistent workgroups, one contiguous range of whole batches each
-  const uint64_t batches = (n + kWinBatch - 1) / kWinBatch;
-  uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * (per_cu > 0 ? per_cu : 1), batches);
-  grid = std::min<uint64_t>(grid, env_cap("ANOMOD_EDGE_WINDOWS_WGS"));
-  a.per_wg = (batches + grid - 1) / grid * kWinBatch;
-  if (a.per_wg > kMaxRange) a.per_wg = kMaxRange;  // (more workgroups than are resident)
-  grid = (n + a.per_wg - 1) / a.per_wg;
+  uint64_t grid = 0;
+  if (int rc = stream_geometry(ctx, edge_windows_kernel, kWinThreads, lds, n,
+                               "ANOMOD_EDGE_WINDOWS_WGS", &a.per_wg, &grid))
+    return rc;
   if (int rc = stage_begin(ctx, kStageEdgeWindows)) return rc;
   ANOMOD_HIP(ctx, hipMemsetAsync(a.misc, 0, b_tab, ctx->stream));
-  if (int rc = span_edge_keys(ctx, spans, S, const_cast<unsigned long long*>(a.keys), ws))
-    return rc;
+  if (int rc = span_edge_keys(ctx, spans, S, keys, ws)) return rc;
   if (int rc = stage_begin(ctx, kStageEdgeWindowKernel)) return rc;
   hipLaunchKernelGGL(edge_windows_kernel, dim3((unsigned)grid), dim3(kWinThreads), lds,
                      ctx->stream, a);
   ANOMOD_HIP(ctx, hipGetLastError());
   if (int rc = stage_end(ctx, kStageEdgeWindowKernel)) return rc;
   if (int rc = stage_end(ctx, kStageEdgeWindows)) return rc;
-  unsigned long long misc[2] = {0ull, 0ull};
-  ANOMOD_HIP(ctx, hipMemcpyAsync(misc, a.misc, 16, hipMemcpyDeviceToHost, ctx->stream));
-  if (out->count)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->count, a.count, TE * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (out->errors)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->errors, a.errors, TE * 8, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-  if (out->sum_us)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->sum_us, a.sum, TE * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (out->max_us)
-    ANOMOD_HIP(ctx, hipMemcpyAsync(out->max_us, a.mx, TE * 4, hipMemcpyDeviceToHost, ctx->stream));
-  ANOMOD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (misc[1]) {
-    set_error(ctx, "edge windows: %llu spans carry no edge key (internal error)", misc[1]);
-    return ANOMOD_ESTATE;
-  }
+  ANOMOD_HIP(ctx, stream_back(ctx, out->count, a.count, TE * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->errors, a.errors, TE * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->sum_us, a.sum, TE * 8));
+  ANOMOD_HIP(ctx, stream_back(ctx, out->max_us, a.mx, TE * 4));
+  unsigned long long misc[2];
+  if (int rc = stream_finish(ctx, a.misc, 1, "edge windows", "key", misc)) return rc;
   out->outside = misc[0];
   return ANOMOD_OK;
 }
