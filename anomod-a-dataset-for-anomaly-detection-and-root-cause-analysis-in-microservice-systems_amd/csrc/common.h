@@ -53,13 +53,14 @@ enum HostSlot { kHostGroupAlloc = ANOMOD_HOST_GROUP_ALLOC, kHostGroupPinned = AN
 // Dense edge stream of a resident set (edge_agg.hip): the layout the set
 // learned from one of its own edge tables — every edge with spans gets a code
 // (its rank among those edges) and the bin range [hist_bin(min), hist_bin(max)]
-// of a cell array — and the u16 code column written through it.  Owned by the
-// set (anomod_spans::dense) and released with it; the device to free on is
-// the one current in free_spans.
+// of a cell array — and the u32 span-word column written through it (code,
+// error bit and duration of every span position: span_word_pack below).  Owned
+// by the set (anomod_spans::dense) and released with it; the device to free on
+// is the one current in free_spans.
 struct DenseSet {
   enum State { kNone = 0,      // this S was looked at and does not fit (or was rejected)
-               kLearned = 1,   // host layout ready, code column not written yet
-               kCoded = 2 };   // layout on the device, code column written
+               kLearned = 1,   // host layout ready, word column not written yet
+               kCoded = 2 };   // layout on the device, word column written
   int state = kNone;
   uint32_t S = 0;              // the service count the layout was learned under
   uint32_t codes = 0, cells = 0;
@@ -71,13 +72,13 @@ struct DenseSet {
   std::vector<uint32_t> host;
   void* dev = nullptr;         // the same on the device + one flag word
   size_t dev_bytes = 0;
-  uint16_t* code = nullptr;    // [n_spans]: code | error << 15; 0xFFFF = no span here
+  uint32_t* word = nullptr;    // [n_spans]: span words of this S; kWordSkip = no span here
   DenseSet() = default;
   DenseSet(const DenseSet&) = delete;
   DenseSet& operator=(const DenseSet&) = delete;
   ~DenseSet() {
     if (dev) (void)hipFree(dev);
-    if (code) (void)hipFree(code);
+    if (word) (void)hipFree(word);
   }
 };
 
@@ -182,9 +183,10 @@ struct anomod_spans {
   mutable uint32_t rows_S = 0;
   mutable uint64_t rows_lo = 0, rows_hi = 0;
   bool keep_rows = true;
-  // Dense edge stream (edge_agg.hip): layout and u16 edge-code column, both
+  // Dense edge stream (edge_agg.hip): layout and u32 span-word column, both
   // functions of the id columns, trace_ptr, svc_flags and the S of the call —
-  // none of which a resident set changes — learned from the set's own table.
+  // none of which a resident set changes (the words also hold dur_us, which it
+  // does not change either) — learned from the set's own table.
   // Only a set that streams its parent rows ever gets one.
   mutable std::unique_ptr<anomod::DenseSet> dense;
 };
@@ -346,5 +348,29 @@ __host__ __device__ inline void hist_bounds(uint32_t bin, uint32_t* lo, uint32_t
   *lo = (uint32_t)(m << e);
   *hi = (uint32_t)(((m + 1) << e) - 1);
 }
+
+// ---- span word of the dense edge stream (edge_agg.hip) -------------------
+// One u32 per span position: code << 22 | error << 21 | duration.  The code
+// field holds every code a layout can own (0 .. 511) and kWordNoCode, which
+// none can: "no span here, skip"; the word of all ones is such a word.  A
+// duration above kWordDurMax does not fit: its field is all ones
+// (kWordDurEscape) and the reader takes dur_us at that position instead, so
+// no result rests on durations being small.
+constexpr uint32_t kWordDurBits = 21, kWordCodeBits = 10;
+constexpr uint32_t kWordErrBit = 1u << kWordDurBits;
+constexpr uint32_t kWordCodeShift = kWordDurBits + 1u;
+constexpr uint32_t kWordDurEscape = (1u << kWordDurBits) - 1u;
+constexpr uint32_t kWordDurMax = kWordDurEscape - 1u;  // the largest duration a word holds
+constexpr uint32_t kWordNoCode = (1u << kWordCodeBits) - 1u;
+constexpr uint32_t kWordSkip = 0xFFFFFFFFu;
+static_assert(kWordCodeBits + 1u + kWordDurBits == 32u, "a span word is 32 bits");
+__host__ __device__ inline uint32_t span_word_pack(uint32_t code, bool error, uint32_t dur) {
+  return code << kWordCodeShift | (error ? kWordErrBit : 0u) |
+         (dur <= kWordDurMax ? dur : kWordDurEscape);
+}
+__host__ __device__ inline uint32_t span_word_code(uint32_t w) { return w >> kWordCodeShift; }
+__host__ __device__ inline bool span_word_error(uint32_t w) { return (w & kWordErrBit) != 0u; }
+// the duration field; kWordDurEscape: read dur_us at the span's position
+__host__ __device__ inline uint32_t span_word_dur(uint32_t w) { return w & kWordDurEscape; }
 
 }  // namespace anomod

@@ -74,7 +74,9 @@ constexpr uint32_t kBins = ANOMOD_HIST_BINS;
 // Experiment-only ablations (never set in the shipped build): 1 = no stats,
 // 2 = no histogram (3 = neither: the span's values are only kept alive, so the
 // record-based streams still load their columns), 4 = no parent lookup, 16 =
-// stream the columns only (the chunk walk).
+// stream the columns only (the chunk walk).  32 / 64 / 96 are 1 / 2 / 3 for
+// edge_dense_kernel alone: the walk and the row stream keep their full tables,
+// so the set still learns its layout and reaches the dense kernel.
 #ifndef ANOMOD_ABL
 #define ANOMOD_ABL 0
 #endif
@@ -1268,106 +1270,136 @@ __global__ __launch_bounds__(kThreads) void edge_row_kernel(
   }
 }
 
-// ---- dense stream: edge codes into a directly indexed histogram -------------
+// ---- dense stream: span words into a directly indexed histogram ------------
 // A resident set touches a sliver of the E x kBins key space, and its own
 // first table says which: every edge with spans gets a code (its rank among
 // those edges) and the bin range [hist_bin(min), hist_bin(max)] of a cell
-// array (DenseSet, common.h).  Once the set's u16 code column is written
-// (edge_encode_kernel: code | error << 15 by span position, 0xFFFF = no span)
-// an aggregation reads that column and dur_us, 6 B/span, and a span costs one
-// 16-B LDS read of its code's entry {min, max, base - first_bin, first_bin |
-// width << 16} — few distinct addresses, mostly a broadcast —, one ds_add_u32
-// on its cell and the per-code stats of the direct form: no hash, no compare
-// chain, no out-of-line insert.  Correctness never rests on the learned
+// array (DenseSet, common.h).  Once the set's u32 span-word column is written
+// (edge_encode_kernel: code, error bit and duration by span position,
+// span_word_pack in common.h; kWordSkip = no span) an aggregation reads that
+// column alone, 4 B/span, and a span costs one 16-B LDS read of its code's
+// entry {min, max, base - first_bin, first_bin | width << 16} — few
+// distinct addresses, mostly a broadcast —, one ds_add_u32 on its cell, one
+// returning ds_add_u32 on a sum replica (u32, by lane; a wrap is a carry
+// counted per code: 64-bit LDS adds cost several times a 32-bit one) and one
+// branch around the rare updates (carry, new extreme, error): no hash, no
+// compare chain, no out-of-line insert.  The kernel is bound by instruction
+// issue, not by LDS or HBM, so what is counted here are instructions per
+// span.  A duration that does not fit its field (the escape value) is read
+// from dur_us by that lane alone.  Correctness never rests on the learned
 // ranges: a span whose bin lies outside its code's range (one unsigned
 // compare) counts in tab.hist in HBM.  Two static LDS carves: small (<= 64
-// codes, <= 8 Ki cells: the SocialNetwork sets) and large (<= 512 codes, <=
-// 32 Ki cells, 4 sum replicas, under 160 KiB).
+// codes, <= 8 Ki cells, 32 sum replicas: the SocialNetwork sets) and large
+// (<= 512 codes, <= 32 Ki cells, 8 sum replicas, under 160 KiB).
 constexpr uint32_t kDenseMaxEdges = 1u << 16;  // edge -> code table: at most 128 KiB
 template <int TIER>
 struct DenseCfg;
 template <>
 struct DenseCfg<0> {
-  static constexpr uint32_t kCodes = 64, kCells = 8192, kReps = 8;
-  static constexpr int kLoad = 2;  // load groups (4 spans each) per thread and round
+  static constexpr uint32_t kCodes = 64, kCells = 8192, kReps = 32;
+  static constexpr int kLoad = 4;  // load groups (4 spans each) per thread and round
 };
 template <>
 struct DenseCfg<1> {
-  static constexpr uint32_t kCodes = 512, kCells = 32768, kReps = 4;
-  static constexpr int kLoad = 4;
+  static constexpr uint32_t kCodes = 512, kCells = 32768, kReps = 8;
+  static constexpr int kLoad = 8;
 };
+static_assert(DenseCfg<1>::kCodes <= kWordNoCode, "the code field holds every code and the skip value");
+static_assert(DenseCfg<0>::kCodes <= DenseCfg<1>::kCodes, "one word format for both tiers");
 template <int TIER>
 struct DenseLds {
   using C = DenseCfg<TIER>;
   static constexpr int kOffEnt = 0;                                       // u32x4 [kCodes]
   static constexpr int kOffCell = kOffEnt + (int)C::kCodes * 16;          // u32 [kCells]
-  static constexpr int kOffSum = kOffCell + (int)C::kCells * 4;           // u64 [kCodes][kReps]
-  static constexpr int kOffErr = kOffSum + (int)(C::kCodes * C::kReps) * 8;  // u32 [kCodes]
-  static constexpr int kBytes = kOffErr + (int)C::kCodes * 4;
+  static constexpr int kOffSum = kOffCell + (int)C::kCells * 4;           // u32 [kCodes][kReps]
+  static constexpr int kOffErr = kOffSum + (int)(C::kCodes * C::kReps) * 4;  // u32 [kCodes]
+  static constexpr int kOffHi = kOffErr + (int)C::kCodes * 4;             // u32 [kCodes]: sum carries
+  static constexpr int kBytes = kOffHi + (int)C::kCodes * 4;
   static_assert(kBytes <= 160 * 1024, "LDS budget");
+  static_assert((C::kReps & (C::kReps - 1u)) == 0u && C::kReps <= (uint32_t)kWave, "replica by lane");
 };
+// hist_bin without its select: below 64 the exponent clamps to 0 and the bin
+// is the value itself (the same bins; clz(0) = 32).
+static_assert(ANOMOD_HIST_SUB_BITS == 5, "values below 2 << SUB_BITS are their own bins");
+__device__ __forceinline__ uint32_t dense_bin(uint32_t v) {
+  constexpr uint32_t kTop = 31u - ANOMOD_HIST_SUB_BITS;
+  const uint32_t z = (uint32_t)__clz((int)v);
+  const uint32_t e = kTop - (z < kTop ? z : kTop);
+  return (e << ANOMOD_HIST_SUB_BITS) + (v >> e);
+}
 constexpr int kDenseSmallWgs = 2;  // workgroups per CU of the small carve
+static_assert(kDenseSmallWgs * DenseLds<0>::kBytes <= 160 * 1024, "LDS budget");
 // Plain row streams of a set between the call that learned its layout and the
-// one that writes the code column.  The column is an investment — a pass of
-// its own (8 B/span read, 2 written: about one row stream) and 2 B/span of
+// one that writes the word column.  The column is an investment — a pass of
+// its own (10 B/span read, 4 written: about one row stream) and 4 B/span of
 // memory — that only a set which keeps being aggregated repays, so it is made
 // at the set's fifth aggregation: the first four calls of every set run
 // exactly the kernels they ran without the dense stream.
 constexpr uint32_t kDenseAfterStreams = 3;
-template <int LOAD>
-struct DenseRegs {
-  u32x4 dr[LOAD];
-  u32x2 cw[LOAD];
-};
 
 // lay: 4 words per code {edge, first_bin, base, width} (DenseSet::host).
 // (the small carve is held to 64 registers: two workgroups per CU)
 template <int TIER>
 __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel(
-    const uint32_t* __restrict__ dur, const uint16_t* __restrict__ code,
+    const uint32_t* __restrict__ dur, const uint32_t* __restrict__ word,
     const u32x4* __restrict__ lay, uint32_t ncodes, uint32_t ncells, uint64_t lo, uint64_t hi,
     Table tab) {
   using C = DenseCfg<TIER>;
   using O = DenseLds<TIER>;
-  using Regs = DenseRegs<C::kLoad>;
   constexpr int kDenseLoad = C::kLoad;
+  struct Regs {
+    u32x4 w[kDenseLoad];
+  };
   __shared__ __attribute__((aligned(16))) unsigned char smem[O::kBytes];
   const int tid = threadIdx.x;
   auto* lent = reinterpret_cast<u32x4*>(smem + O::kOffEnt);
   auto* lent1 = reinterpret_cast<uint32_t*>(smem + O::kOffEnt);
   auto* lcell = reinterpret_cast<uint32_t*>(smem + O::kOffCell);
-  auto* lsum = reinterpret_cast<unsigned long long*>(smem + O::kOffSum);
+  auto* lsum = reinterpret_cast<uint32_t*>(smem + O::kOffSum);
   auto* lerr = reinterpret_cast<uint32_t*>(smem + O::kOffErr);
+  auto* lhi = reinterpret_cast<uint32_t*>(smem + O::kOffHi);
   for (uint32_t c = tid; c < ncodes; c += kThreads) {
     const u32x4 l = lay[c];
     lent[c] = u32x4{0xFFFFFFFFu, 0u, l.z - l.y, l.y | (l.w << 16)};
     lerr[c] = 0u;
+    lhi[c] = 0u;
   }
   for (uint32_t k = tid; k < ncells; k += kThreads) lcell[k] = 0u;
-  for (uint32_t k = tid; k < ncodes * C::kReps; k += kThreads) lsum[k] = 0ull;
+  for (uint32_t k = tid; k < ncodes * C::kReps; k += kThreads) lsum[k] = 0u;
   __syncthreads();
-  // cw: code | error << 15.  A code past the layout's (0xFFFF: no span here)
-  // is skipped, so no index below leaves the carve.
-  auto one = [&](uint32_t d, uint32_t cw) {
-    const uint32_t c = cw & 0x7FFFu;
+  const uint32_t rep = __lane_id() & (C::kReps - 1u);
+  // w: the span word of position g.  A code past the layout's (kWordNoCode: no
+  // span here) is skipped, so no index below leaves the carve; the escape load
+  // is taken by the lanes that need it only.
+  auto one = [&](uint32_t w, uint64_t g) {
+    const uint32_t c = span_word_code(w);
     if (c >= ncodes) return;
-    if constexpr ((ANOMOD_ABL & 3) == 3) {  // keep the loads, do nothing
-      if ((cw ^ d) == 0x9E3779B9u) tab.err[0] = d;
+    if constexpr ((ANOMOD_ABL & 96) == 96) {  // keep the loads, do nothing
+      if (w == 0x9E3779B9u) tab.err[0] = w;
       return;
     }
+    uint32_t d = span_word_dur(w);
+    if (__builtin_expect(d == kWordDurEscape, 0)) d = dur[g];
     const u32x4 e = lent[c];
-    const uint32_t bin = hist_bin(d);
-    if constexpr (!(ANOMOD_ABL & 2)) {
+    const uint32_t bin = dense_bin(d);
+    if constexpr (!(ANOMOD_ABL & 64)) {
       if (bin - (e.w & 0xFFFFu) < (e.w >> 16))
         atomicAdd(&lcell[e.z + bin], 1u);
       else
         atomicAdd(&tab.hist[(uint64_t)lay[c].x * kBins + bin], 1ull);
     }
-    if constexpr (!(ANOMOD_ABL & 1)) {
-      atomicAdd(&lsum[c * C::kReps + (__lane_id() & (C::kReps - 1u))], (unsigned long long)d);
-      if (d < e.x) atomicMin(&lent1[4u * c], d);
-      if (d > e.y) atomicMax(&lent1[4u * c + 1u], d);
-      if (cw & 0x8000u) atomicAdd(&lerr[c], 1u);
+    if constexpr (!(ANOMOD_ABL & 32)) {
+      // the sum in u32 replicas: an add that wraps its replica (seen in the
+      // value it returns) counts a carry of 2^32 for the code
+      const uint32_t before = atomicAdd(&lsum[c * C::kReps + rep], d);
+      const bool carry = before + d < d, err = span_word_error(w);
+      // one branch around the four rare updates
+      if (__builtin_expect(carry | err | (d < e.x) | (d > e.y), 0)) {
+        if (carry) atomicAdd(&lhi[c], 1u);
+        if (d < e.x) atomicMin(&lent1[4u * c], d);
+        if (d > e.y) atomicMax(&lent1[4u * c + 1u], d);
+        if (err) atomicAdd(&lerr[c], 1u);
+      }
     }
   };
   const uint64_t up = (lo + 3ull) & ~3ull;
@@ -1375,21 +1407,19 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
   const uint64_t a1 = (hi & ~3ull) > a0 ? (hi & ~3ull) : a0;  // groups [a0, a1), tail [a1, hi)
   if (blockIdx.x == 0 && tid < 8) {
     const uint64_t g = tid < 4 ? lo + (uint64_t)tid : a1 + (uint64_t)(tid - 4);
-    if (g < (tid < 4 ? a0 : hi)) one(dur[g], code[g]);
+    if (g < (tid < 4 ? a0 : hi)) one(word[g], g);
   }
   const uint64_t ng = (a1 - a0) / 4;
-  const u32x4* dr4 = reinterpret_cast<const u32x4*>(dur + a0);
-  const u32x2* cw2 = reinterpret_cast<const u32x2*>(code + a0);
+  const u32x4* w4 = reinterpret_cast<const u32x4*>(word + a0);
   // groups past the end re-read the last one (no branch around a load) and
-  // take skip codes
+  // take skip words
   auto load = [&](uint64_t g0, Regs& R) {
 #pragma unroll
     for (int j = 0; j < kDenseLoad; ++j) {
       const uint64_t gi = g0 + (uint64_t)(j * kThreads + tid);
       const uint64_t gc = gi < ng ? gi : ng - 1;
-      R.dr[j] = dr4[gc];
-      const u32x2 w = cw2[gc];
-      R.cw[j] = gi < ng ? w : u32x2{0xFFFFFFFFu, 0xFFFFFFFFu};
+      const u32x4 w = w4[gc];
+      R.w[j] = gi < ng ? w : u32x4{kWordSkip, kWordSkip, kWordSkip, kWordSkip};
     }
   };
   constexpr uint64_t kPerBlock = (uint64_t)kThreads * kDenseLoad;
@@ -1402,10 +1432,11 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     if (gn < ng) load(gn, nxt);
 #pragma unroll
     for (int j = 0; j < kDenseLoad; ++j) {
-      one(cur.dr[j].x, cur.cw[j].x & 0xFFFFu);
-      one(cur.dr[j].y, cur.cw[j].x >> 16);
-      one(cur.dr[j].z, cur.cw[j].y & 0xFFFFu);
-      one(cur.dr[j].w, cur.cw[j].y >> 16);
+      const uint64_t g = a0 + 4ull * (g0 + (uint64_t)(j * kThreads + tid));
+      one(cur.w[j].x, g);
+      one(cur.w[j].y, g + 1);
+      one(cur.w[j].z, g + 2);
+      one(cur.w[j].w, g + 3);
     }
     cur = nxt;
     g0 = gn;
@@ -1426,7 +1457,7 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     const u32x4 e = lent[c];
     if (e.x != 0xFFFFFFFFu || e.y != 0u) {
       const uint32_t edge = lay[c].x;
-      unsigned long long sum = 0;
+      unsigned long long sum = (unsigned long long)lhi[c] << 32;
       for (uint32_t k = 0; k < C::kReps; ++k) sum += lsum[c * C::kReps + k];
       atomicAdd(&tab.sum[edge], sum);
       if (lerr[c]) atomicAdd(&tab.err[edge], (unsigned long long)lerr[c]);
@@ -1436,39 +1467,44 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
   }
 }
 
-// The code column of spans [lo, hi) from the parent rows and svc_flags through
-// the edge -> code table (e2c, u16 per edge, 0xFFFF = the layout has no code
-// for this edge: *bad is set and the set stays on the row stream).  Four span
-// positions per thread; positions outside [lo, hi) are left alone.
+// The span-word column of spans [lo, hi) from the parent rows, svc_flags and
+// dur_us through the edge -> code table (e2c, u16 per edge, 0xFFFF = the
+// layout has no code for this edge: *bad is set and the set stays on the row
+// stream).  Four span positions per thread; positions outside [lo, hi) are
+// left alone.
 __global__ __launch_bounds__(256) void edge_encode_kernel(
-    const uint32_t* __restrict__ svcfl, const uint16_t* __restrict__ rows,
-    const uint16_t* __restrict__ e2c, uint16_t* __restrict__ code, uint64_t lo, uint64_t hi,
-    uint32_t S, uint32_t S0, uint32_t* __restrict__ bad) {
+    const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
+    const uint16_t* __restrict__ rows, const uint16_t* __restrict__ e2c,
+    uint32_t* __restrict__ word, uint64_t lo, uint64_t hi, uint32_t S, uint32_t S0,
+    uint32_t* __restrict__ bad) {
   const uint64_t q0 = lo & ~3ull;
   const uint64_t nq = (hi - q0 + 3ull) / 4ull;
-  auto enc = [&](uint32_t sf, uint32_t row) -> uint32_t {
-    if (row == 0xFFFFu) return 0xFFFFu;
+  auto enc = [&](uint32_t sf, uint32_t d, uint32_t row) -> uint32_t {
+    if (row == 0xFFFFu) return kWordSkip;
     const uint32_t p = row >= S0 ? row - S0 + S : row;
     const uint32_t c = e2c[p * S + (sf & 0xFFFFu)];
     if (c == 0xFFFFu) {
       *bad = 1u;
-      return 0xFFFFu;
+      return kWordSkip;
     }
-    return c | ((sf >> 16) & ANOMOD_FLAG_ERROR ? 0x8000u : 0u);
+    return span_word_pack(c, ((sf >> 16) & ANOMOD_FLAG_ERROR) != 0u, d);
   };
   for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq;
        q += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t g = q0 + 4ull * q;
     if (g >= lo && g + 4ull <= hi) {
       const u32x4 sf = *reinterpret_cast<const u32x4*>(svcfl + g);
+      const u32x4 dr = *reinterpret_cast<const u32x4*>(dur + g);
       const u32x2 rw = *reinterpret_cast<const u32x2*>(rows + g);
-      u32x2 out;
-      out.x = enc(sf.x, rw.x & 0xFFFFu) | (enc(sf.y, rw.x >> 16) << 16);
-      out.y = enc(sf.z, rw.y & 0xFFFFu) | (enc(sf.w, rw.y >> 16) << 16);
-      *reinterpret_cast<u32x2*>(code + g) = out;
+      u32x4 out;
+      out.x = enc(sf.x, dr.x, rw.x & 0xFFFFu);
+      out.y = enc(sf.y, dr.y, rw.x >> 16);
+      out.z = enc(sf.z, dr.z, rw.y & 0xFFFFu);
+      out.w = enc(sf.w, dr.w, rw.y >> 16);
+      *reinterpret_cast<u32x4*>(word + g) = out;
     } else {
       for (uint64_t i = g < lo ? lo : g; i < g + 4ull && i < hi; ++i)
-        code[i] = (uint16_t)enc(svcfl[i], rows[i]);
+        word[i] = enc(svcfl[i], dur[i], rows[i]);
     }
   }
 }
@@ -1856,8 +1892,8 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
 }
 
 // The transition call of a learned layout.  dense_alloc: device room for the layout and
-// the code column (false: an allocation failed, the set stays on the row
-// stream).  dense_encode: the layout to the device and the code column of
+// the word column (false: an allocation failed, the set stays on the row
+// stream).  dense_encode: the layout to the device and the word column of
 // [rows_lo, rows_hi), queued after the row stream of this call; the flag word
 // comes back into *h_bad with the table.
 bool dense_alloc(anomod_ctx* ctx, const anomod_spans* s) {
@@ -1874,13 +1910,13 @@ bool dense_alloc(anomod_ctx* ctx, const anomod_spans* s) {
     }
     d.dev_bytes = bytes;
   }
-  if (!d.code) {
+  if (!d.word) {
     void* p = nullptr;
-    if (dev_malloc(ctx, &p, s->n_spans * 2) != hipSuccess) {
+    if (dev_malloc(ctx, &p, s->n_spans * 4) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
-    d.code = static_cast<uint16_t*>(p);
+    d.word = static_cast<uint32_t*>(p);
   }
   return true;
 }
@@ -1896,8 +1932,8 @@ int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h
   if (nq) {
     const uint64_t blocks = std::min<uint64_t>((nq + 255) / 256, 64ull * ctx->num_cus);
     hipLaunchKernelGGL(edge_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
-                       s->svc_flags, s->parent_row,
-                       reinterpret_cast<const uint16_t*>(base + 4u * d.codes), d.code, s->rows_lo,
+                       s->svc_flags, s->dur_us, s->parent_row,
+                       reinterpret_cast<const uint16_t*>(base + 4u * d.codes), d.word, s->rows_lo,
                        s->rows_hi, S, s->rows_S, d_bad);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
@@ -1924,7 +1960,7 @@ int launch_dense(anomod_ctx* ctx, const anomod_spans* s, const Table& tab) {
     const uint64_t b = std::min<uint64_t>(s->rows_hi, a + cap);
     const uint64_t want = (b - a + kRound - 1) / kRound;
     const uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * per_cu, want);
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->dur_us, d.code,
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->dur_us, d.word,
                        static_cast<const u32x4*>(d.dev), d.codes, d.cells, a, b, tab);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
@@ -2292,8 +2328,8 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   // Dense stream (edge_dense_kernel).  Whatever call learned a layout for
   // this S (`build`, or a row stream under another layout's S) is followed by
   // kDenseAfterStreams plain row streams, then by one that also writes the
-  // code column (`dense_enc`), and from then on the set's aggregations at
-  // this S read codes and durations only (`dense_run`).  A call with another
+  // span-word column (`dense_enc`), and from then on the set's aggregations at
+  // this S read that column only (`dense_run`).  A call with another
   // S goes back to the row stream and learns that S's layout.
   const bool dense_try = rows_ok && dense_allowed();
   DenseSet* ds = spans->dense.get();

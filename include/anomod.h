@@ -188,12 +188,14 @@ int anomod_spans_set_hints(anomod_spans* spans, int scan_order, int hist_form);
  * ANOMOD_ESTATE when the set holds none: no aggregation yet, a call run with
  * ANOMOD_PARENT_ROWS=0 / ANOMOD_HIST_FORM / ANOMOD_UNIQUE_SCAN set, an
  * ungrouped set, or the column could not be allocated.
- * A set that streams its rows may also keep a second derived column, the u16
- * edge codes of the dense stream (2 B/span more, written by the set's fifth
+ * A set that streams its rows may also keep a second derived column, the u32
+ * span words of the dense stream (edge code, error bit and duration of every
+ * span position; 4 B/span more, written by the set's fifth
  * aggregation at a service count when the edges and histogram bins its first
  * table touched fit a directly indexed LDS histogram: at most 512 edges with
  * spans and 32 Ki bins in their ranges); its aggregations from the sixth on
- * then read codes and durations, 6 B/span.  Same tables bit for bit;
+ * then read that column alone, 4 B/span (a duration that does not fit a
+ * word's 21-bit field is read from dur_us).  Same tables bit for bit;
  * ANOMOD_EDGE_DENSE=0 switches it off, everything that bypasses the rows
  * bypasses it, and this column keeps its encoding and every other reader.   */
 int anomod_spans_parent_rows(anomod_ctx* ctx, const anomod_spans* spans, uint16_t* out_host,
