@@ -17,8 +17,9 @@ from .decode import (MetricMatrix, decode_jaeger, decode_native, load_trace_file
                      jaeger_span_rows, merge_jaeger_dumps, skywalking_parents)
 from .device import (Context, DeviceGraph, DeviceSeries, DeviceSpans, SynthSpec, device_count,
                      device_count_safe, synth_generate_host, synth_graph_csr, synth_services)
-from .engine import (Experiment, Features, default_context, fault_target, features, hit_at,
-                     load_experiment, load_window_scores, rank, trace_window_scores)
+from .engine import (Experiment, Features, SymptomCorrelation, default_context, fault_target,
+                     features, hit_at, load_experiment, load_window_scores, rank,
+                     trace_window_scores, walk_graph)
 from . import api
 from .segments import SegmentSet, service_name_of, trace_infos
 from .writers import jaeger_to_csv, write_jaeger_csv, write_metric_long_csv
@@ -38,6 +39,7 @@ __all__ = [
     "jaeger_to_csv", "write_jaeger_csv", "write_metric_long_csv", "decode_native",
     "load_trace_file", "api", "trace_window_scores", "TraceSpectrum", "spectrum_thresholds",
     "CriticalPath", "TraceShapes", "ErrorOrigins", "EdgeLoad", "EdgeExemplars", "load_window_scores",
+    "SymptomCorrelation", "walk_graph",
 ]
 
 

@@ -2,6 +2,7 @@
                                  [--spectrum] [--critical-path] [--shapes]
                                  [--error-origins] [--trace-step S [--trace-load]]
                                  [--exemplars K]
+                                 [--trace-step S --symptom-corr [--walk correlation]]
                                  [--baseline <trace file|dir>]
        python -m anomod jaeger-to-csv <all_traces.json> <all_traces.csv>
 
@@ -72,6 +73,19 @@ def edge_load_doc(load) -> dict:
                      "carried": [int(v) for v in load.carried[:, r]]})
     return {"t0_us": int(load.t0_us), "step_us": int(load.step_us),
             "windows": int(load.n_windows), "outside": int(load.outside), "edges": rows}
+
+
+def _key_doc(key) -> dict:
+    labels = key[1] if len(key) > 1 else ()
+    return {"name": str(key[0]), "labels": {str(k): str(v) for k, v in labels}}
+
+
+def symptom_correlates_doc(sc, top: int = 10) -> list[dict]:
+    """The "symptom_correlates" list of the features JSON: the `top` trace
+    columns and metric series that move most with the front-door latency:
+    {kind ("trace" | "metric"), name, labels, r, n (common windows)}."""
+    return [{"kind": row["kind"], **_key_doc(row["key"]), "r": row["r"], "n": row["n"]}
+            for row in sc.top(top)]
 
 
 def _exemplar_calls(ex, spans, row: int, names: dict) -> list[dict]:
@@ -167,6 +181,14 @@ def main(argv=None) -> int:
                    help="also list, for each of the top 5 ranked services, the K slowest calls "
                         "of its slowest incoming edge and the K slowest failed calls of its "
                         "most failing one, with their trace ids, as \"exemplars\" (K in 1..64)")
+    f.add_argument("--symptom-corr", action="store_true",
+                   help="with --trace-step: correlate every edge's latency series and every "
+                        "metric series with the front-door latency series and write the "
+                        "per-service result as \"symptom_corr\" and the ten strongest "
+                        "columns as \"symptom_correlates\"")
+    f.add_argument("--walk", choices=("calls", "correlation"), default="calls",
+                   help="what weights the ranking's walk: call counts, or (with "
+                        "--symptom-corr) how each service follows the front-door latency")
     f.add_argument("--baseline", metavar="TRACES",
                    help="trace file (or dir) of a normal run: its features are the baseline "
                         "of the latency term and of the spectrum's latency thresholds")
@@ -182,6 +204,10 @@ def main(argv=None) -> int:
 
     if args.trace_load and args.trace_step is None:
         ap.error("--trace-load needs --trace-step")
+    if args.symptom_corr and args.trace_step is None:
+        ap.error("--symptom-corr needs --trace-step")
+    if args.walk == "correlation" and not args.symptom_corr:
+        ap.error("--walk correlation needs --symptom-corr")
     exp = load_experiment(args.traces, metrics=args.metrics)
     baseline = None
     if args.baseline:
@@ -192,8 +218,9 @@ def main(argv=None) -> int:
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
                      critical_path=args.critical_path, trace_quantile=args.trace_quantile,
                      shapes=args.shapes, error_origins=args.error_origins,
-                     trace_load=args.trace_load, exemplars=args.exemplars)
-    ranking = rank(feats, alpha=args.alpha)
+                     trace_load=args.trace_load, exemplars=args.exemplars,
+                     symptom_corr=args.symptom_corr)
+    ranking = rank(feats, walk=args.walk, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
         "label": exp.label,
@@ -233,6 +260,10 @@ def main(argv=None) -> int:
         doc["edge_load"] = edge_load_doc(feats.edge_load)
         doc["load_scores"] = dict(zip(feats.edges.services,
                                       map(float, feats.params["components"]["load"])))
+    if feats.symptom_corr is not None:
+        doc["symptom_corr"] = dict(zip(feats.edges.services,
+                                       map(float, feats.symptom_corr.service)))
+        doc["symptom_correlates"] = symptom_correlates_doc(feats.symptom_corr)
     if feats.exemplars is not None:
         doc["exemplars"] = exemplars_doc(feats, exp.spans, ranking,
                                          trace_file=exp.meta.get("trace_file"))

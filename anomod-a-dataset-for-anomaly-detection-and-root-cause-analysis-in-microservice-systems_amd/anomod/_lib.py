@@ -19,6 +19,7 @@ HIST_SUB_BITS = 5
 HIST_BINS = 896
 ROOT_ROWS = 2
 FLAG_ERROR = 0x1
+CORR_MAX_TARGETS = 8
 UNIQUE_ID_BYTES = 128
 TOPO_SN = 0
 TOPO_TT = 1
@@ -30,7 +31,8 @@ _STATUS = {EINVAL: "EINVAL", EHIP: "EHIP", ERCCL: "ERCCL", ENOMEM: "ENOMEM", EST
 (STAGE_EDGE_AGG, STAGE_EDGE_FINAL, STAGE_EDGE_REDUCE, STAGE_EWMA, STAGE_PAGERANK,
  STAGE_TRACE_STRUCT, STAGE_SEGMENTS, STAGE_SUMMARY, STAGE_GROUP,
  STAGE_EDGE_WINDOWS, STAGE_EDGE_WINDOW_KERNEL, STAGE_EDGE_LOAD, STAGE_EDGE_LOAD_KERNEL,
- STAGE_EDGE_LOAD_SCAN, STAGE_EDGE_EXEMPLARS, STAGE_EDGE_EXEMPLARS_KERNEL) = range(16)
+ STAGE_EDGE_LOAD_SCAN, STAGE_EDGE_EXEMPLARS, STAGE_EDGE_EXEMPLARS_KERNEL,
+ STAGE_SERIES_CORR) = range(17)
 (HOST_GROUP_ALLOC, HOST_GROUP_PINNED, HOST_GROUP_WALL, HOST_UPLOAD_SETUP,
  HOST_SET_ALLOC) = range(5)
 HOST_SLOTS = 5
@@ -337,6 +339,9 @@ _SIGS = {
     "anomod_series_download": (_i32, [_vp, _vp, _P(_f32)]),
     "anomod_series_ewma_z": (_i32, [_vp, _vp, _f32, _u32, _f32, _P(_f32)]),
     "anomod_series_free": (_i32, [_vp]),
+    "anomod_series_correlate": (_i32, [_vp, _vp, _P(_f32), _u32, _u32, _P(_f64), _P(_u32)]),
+    "anomod_correlate": (_i32, [_vp, _P(_f32), _u64, _u64, _P(_f32), _u32, _u32, _P(_f64),
+                                _P(_u32)]),
     "anomod_pagerank": (_i32, [_vp, _P(_u32), _P(_u32), _P(_f32), _u32, _P(_f64), _f64, _u32,
                                _f64, _P(_f64), _P(_u32)]),
     "anomod_graph_create": (_i32, [_vp, _P(_u32), _P(_u32), _P(_f32), _u32, _P(_vp)]),

@@ -777,6 +777,24 @@ class Context:
                                             eps, L.ptr(Z, C.c_float)))
         return Z
 
+    def correlate(self, X: np.ndarray, Y: np.ndarray, min_pairs: int = 3
+                  ) -> tuple[np.ndarray, np.ndarray]:
+        """Pearson correlation of every column of X [T, S] against the target
+        columns Y [T, K] (a 1-D Y is one target; K <= 8), pairwise-complete
+        over non-finite samples (anomod_correlate; the contract is in
+        include/anomod.h).  Returns (r f64 [K, S], n u32 [K, S]): r is NaN
+        where fewer than max(min_pairs, 2) pairs exist or a side is constant."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        Y = _targets(Y, X.shape[0])
+        T, S = X.shape
+        K = Y.shape[1]
+        r = np.full((K, S), np.nan, np.float64)
+        n = np.zeros((K, S), np.uint32)
+        self._check(self._lib.anomod_correlate(self.handle, L.ptr(X, C.c_float), T, S,
+                                               L.ptr(Y, C.c_float), K, int(min_pairs),
+                                               L.ptr(r, C.c_double), L.ptr(n, C.c_uint32)))
+        return r, n
+
     # -- ranking
     def pagerank(self, row_ptr, col, w, p, alpha=0.85, iters=100, tol=1e-10):
         row_ptr = np.ascontiguousarray(row_ptr, np.uint32)
@@ -793,6 +811,16 @@ class Context:
                                               L.ptr(p, C.c_double), alpha, iters, tol,
                                               L.ptr(x, C.c_double), C.byref(done)))
         return x, done.value
+
+
+def _targets(Y, T: int) -> np.ndarray:
+    """Correlation targets as a C-contiguous f32 [T, K] (a 1-D Y is K = 1)."""
+    Y = np.asarray(Y, dtype=np.float32)
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.ndim != 2 or Y.shape[0] != T:
+        raise ValueError(f"correlate: Y of shape {Y.shape} does not hold T={T} rows")
+    return np.ascontiguousarray(Y)
 
 
 def synth_graph_csr(N: int, mean_degree: int = 10, seed: int = 11):
@@ -929,6 +957,18 @@ class DeviceSeries:
             self.ctx.handle, self.handle, alpha, W, eps,
             L.ptr(Z, C.c_float) if Z is not None else C.cast(None, C.POINTER(C.c_float))))
         return Z
+
+    def correlate(self, Y: np.ndarray, min_pairs: int = 3) -> tuple[np.ndarray, np.ndarray]:
+        """Context.correlate of the resident matrix (anomod_series_correlate):
+        reads it in the layout it has and leaves it and the EWMA state alone."""
+        Y = _targets(Y, self.T)
+        K = Y.shape[1]
+        r = np.full((K, self.S), np.nan, np.float64)
+        n = np.zeros((K, self.S), np.uint32)
+        self.ctx._check(L.lib().anomod_series_correlate(
+            self.ctx.handle, self.handle, L.ptr(Y, C.c_float), K, int(min_pairs),
+            L.ptr(r, C.c_double), L.ptr(n, C.c_uint32)))
+        return r, n
 
     def free(self):
         if self.handle:

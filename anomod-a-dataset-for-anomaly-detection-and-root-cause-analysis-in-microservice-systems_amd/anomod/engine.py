@@ -9,7 +9,10 @@ on the GPU:
   errors, p50/p99;
 * window scores: libanomod EWMA/z kernel over the metric matrix;
 * ranking: libanomod personalized PageRank over the caller -> callee graph,
-  seeded by per-service anomaly scores.
+  seeded by per-service anomaly scores;
+* symptom correlation: libanomod series correlation of the per-edge trace
+  series and the metric series against the front-door latency series, which
+  can weight the walk (rank(walk="correlation")).
 """
 from __future__ import annotations
 
@@ -155,6 +158,41 @@ def load_experiment(source, *, metrics=None, name: str | None = None,
 
 
 @dataclass
+class SymptomCorrelation:
+    """features(symptom_corr=True): how every trace series and every metric
+    series moves with the front-door latency (EdgeWindows.symptom).  r is the
+    Pearson correlation over the windows where both are present (n of them;
+    NaN below min_pairs or for a constant side: Context.correlate)."""
+
+    services: list[str]
+    symptom: np.ndarray                    # f32 [T] on the trace windows
+    keys: list                             # the correlated columns of win.matrix()
+    r: np.ndarray                          # f64 [len(keys)]
+    n: np.ndarray                          # u32 [len(keys)]
+    service: np.ndarray                    # f64 [S] in [0, 1]: max r over incoming edges
+    # the metric part: "regular" (computed), "irregular" or "none" (skipped)
+    metric_grid: str = "none"
+    metric_rows: tuple[int, int] | None = None   # metric rows [i0, i1] it covers
+    metric_symptom: np.ndarray | None = None     # f32 on those rows
+    metric_keys: list | None = None              # the metric series
+    metric_r: np.ndarray | None = None
+    metric_n: np.ndarray | None = None
+    metric_service: np.ndarray | None = None     # f64 [S]: max |r| over a service's series
+
+    def top(self, k: int = 10) -> list[dict]:
+        """The k columns / series of largest |r| (NaN left out; ties by
+        position, trace columns first): {"kind": "trace" | "metric", "key",
+        "r", "n"}."""
+        rows = [("trace", key, float(r), int(n)) for key, r, n in zip(self.keys, self.r, self.n)]
+        if self.metric_keys is not None:
+            rows += [("metric", key, float(r), int(n))
+                     for key, r, n in zip(self.metric_keys, self.metric_r, self.metric_n)]
+        rows = [row for row in rows if row[2] == row[2]]
+        rows.sort(key=lambda row: -abs(row[2]))
+        return [{"kind": kind, "key": key, "r": r, "n": n} for kind, key, r, n in rows[:max(0, k)]]
+
+
+@dataclass
 class Features:
     experiment: str
     edges: EdgeTable
@@ -182,6 +220,8 @@ class Features:
     # slowest error-flagged ones
     exemplars: EdgeExemplars | None = None
     error_exemplars: EdgeExemplars | None = None
+    # features(symptom_corr=True): correlation with the front-door latency
+    symptom_corr: SymptomCorrelation | None = None
 
 
 _default_ctx: Context | None = None
@@ -320,19 +360,98 @@ def _trace_load(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float
 
 def _trace_windows(spans: SpanSet, ctx: Context, step_s: float, W: int, eps: float,
                    min_count: int, quantile: int | None = None
-                   ) -> tuple[EdgeWindows, np.ndarray]:
+                   ) -> tuple[EdgeWindows, np.ndarray, decode.MetricMatrix]:
+    """The per-window edge table, its per-service score and win.matrix() (not
+    padded) the score was taken from."""
     t0, step_us, T = _trace_range(spans, step_s)
     S = spans.n_services
     if quantile is None:
         win = ctx.edge_windows(spans, t0, step_us, T)
-        mm = win.matrix(min_count).pad_to_multiple(W)
+        mm0 = win.matrix(min_count)
     else:
         win = ctx.edge_window_quantiles(spans, t0, step_us, T, q_pct=(int(quantile),))
-        mm = win.matrix(min_count, quantile=int(quantile)).pad_to_multiple(W)
+        mm0 = win.matrix(min_count, quantile=int(quantile))
+    mm = mm0.pad_to_multiple(W)
     if mm.S == 0 or mm.T == 0:
-        return win, np.zeros(S)
+        return win, np.zeros(S), mm0
     Z = ctx.ewma_z(mm.X, 2.0 / (W + 1), W, eps)
-    return win, trace_window_scores(Z, win, S, 2 if quantile is None else 3)
+    return win, trace_window_scores(Z, win, S, 2 if quantile is None else 3), mm0
+
+
+def _labels_service(series: list, services: list[str]) -> np.ndarray:
+    """Service index of every series (-1: none) by _series_service, decided
+    once per distinct label set (a TT matrix holds ~6 k series over ~50 label
+    sets)."""
+    memo: dict = {}
+    labs = [k[1] if len(k) > 1 else () for k in series]
+    if not all(isinstance(lb, tuple) for lb in labs):  # a caller's lists of pairs
+        labs = [lb if isinstance(lb, tuple) else tuple(tuple(kv) for kv in lb) for lb in labs]
+    by_labels = {}
+    for lb in dict.fromkeys(labs):
+        i = _series_service(("", lb), services, memo)
+        by_labels[lb] = -1 if i is None else i
+    return np.fromiter(map(by_labels.__getitem__, labs), np.int64, len(labs))
+
+
+def _metric_grid(metrics: "decode.MetricMatrix | None") -> str:
+    """"regular" when the metric matrix has T >= 2 rows whose consecutive
+    timestamp differences are all equal and positive, "irregular" when it has
+    rows that are not, "none" without a matrix."""
+    if metrics is None or metrics.S == 0 or metrics.T == 0:
+        return "none"
+    d = np.diff(np.asarray(metrics.timestamps, np.float64))
+    return "regular" if d.size >= 1 and d[0] > 0 and bool((d == d[0]).all()) else "irregular"
+
+
+def _symptom_correlation(exp: Experiment, ctx: Context, win: EdgeWindows,
+                         mm0: "decode.MetricMatrix", min_count: int, min_pairs: int
+                         ) -> SymptomCorrelation:
+    spans, services = exp.spans, win.services
+    S = len(services)
+    y = win.symptom(min_count)
+    per_edge = 3 if any(k[0].startswith("edge_p") for k in mm0.series) else 2
+    cols = np.array([j for j, k in enumerate(mm0.series) if k[0] != "edge_count"], np.int64)
+    keys = [mm0.series[j] for j in cols.tolist()]
+    svc = np.zeros(S)
+    if cols.size and y.shape[0]:
+        r, n = ctx.correlate(mm0.X[:, cols], y, min_pairs)
+        r, n = r[0], n[0]
+        # the rule of trace_window_scores: a service takes the max over the
+        # columns of the edges it is the child of; NaN and negative r count as 0
+        active = np.nonzero(win.count.sum(axis=0))[0]
+        child = (active % S)[cols // per_edge]
+        np.fmax.at(svc, child, np.where(r > 0, r, 0.0))
+    else:
+        r, n = np.zeros(0), np.zeros(0, np.uint32)
+    sc = SymptomCorrelation(list(services), y, keys, r, n, svc, _metric_grid(exp.metrics))
+    if sc.metric_grid != "regular":
+        return sc
+    # the front-door series again, on the metric grid: metric row i covers
+    # [ts[i], ts[i] + step); the rows that touch the trace start range
+    ts = np.asarray(exp.metrics.timestamps, np.float64)
+    step_us = max(1, int(round((ts[1] - ts[0]) * 1e6)))
+    ts_us = np.rint(ts * 1e6).astype(np.int64)
+    nz = spans.start_us[spans.start_us != 0]
+    sc.metric_keys = list(exp.metrics.series)
+    sc.metric_r = np.full(exp.metrics.S, np.nan)
+    sc.metric_n = np.zeros(exp.metrics.S, np.uint32)
+    sc.metric_service = np.zeros(S)
+    hit = (np.nonzero((ts_us + step_us > int(nz.min())) & (ts_us <= int(nz.max())))[0]
+           if nz.size else np.zeros(0, np.int64))
+    if hit.size == 0:
+        return sc
+    i0 = int(hit[0])
+    Tm = min(int(hit[-1]) - i0 + 1, MAX_TRACE_WINDOWS, MAX_TRACE_CELLS // max(1, edge_rows(S)))
+    if Tm < 1:
+        return sc
+    win_m = ctx.edge_windows(spans, int(ts_us[i0]), step_us, Tm)
+    ym = win_m.symptom(min_count)
+    rm, nm = ctx.correlate(exp.metrics.X[i0:i0 + Tm], ym, min_pairs)
+    sc.metric_rows, sc.metric_symptom, sc.metric_r, sc.metric_n = (i0, i0 + Tm - 1), ym, rm[0], nm[0]
+    idx = _labels_service(sc.metric_keys, services)
+    ok = idx >= 0
+    np.fmax.at(sc.metric_service, idx[ok], np.abs(rm[0])[ok])  # a metric's sign is arbitrary
+    return sc
 
 
 def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
@@ -343,7 +462,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              spectrum_rows: str = "root", critical_path: bool = False,
              trace_quantile: int | None = None, shapes: bool = False,
              error_origins: bool = False, trace_load: bool = False,
-             exemplars: int | None = None) -> Features:
+             exemplars: int | None = None, symptom_corr: bool = False,
+             corr_min_pairs: int = 3) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -390,12 +510,27 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     edge and the K slowest error-flagged ones (Context.edge_exemplars:
     Features.exemplars / .error_exemplars) — the way from a ranked service
     back to the traces that show it; no score or component changes.
+    With symptom_corr (needs trace_step_s) every trace series of win.matrix()
+    except the call counts is correlated (Context.correlate, at least
+    corr_min_pairs common windows) with the front-door latency series
+    (EdgeWindows.symptom(trace_min_count)); a service takes the max over the
+    columns of the edges it is the child of, NaN and negative r as 0
+    (components["symptom_corr"], in [0, 1]).  With a metric matrix on a
+    regular grid (params["metric_corr_grid"] = "regular"; "irregular" and
+    "none" skip this part) the front-door series is taken again on the metric
+    rows that touch the trace start range, every metric series is correlated
+    with it and a service takes the max |r| of its series
+    (components["metric_corr"]).  Features.symptom_corr holds both with the
+    per-column r and n; rank(walk="correlation") walks by them.  No score or
+    other component changes.
     Non-finite window scores: a column whose score is NaN is skipped, +inf
     squashes to 1, so service_scores stays finite."""
     if trace_load and trace_step_s is None:
         raise ValueError("features(trace_load=True) needs trace_step_s")
     if trace_quantile is not None and trace_step_s is None:
         raise ValueError("features(trace_quantile=...) needs trace_step_s")
+    if symptom_corr and trace_step_s is None:
+        raise ValueError("features(symptom_corr=True) needs trace_step_s")
     if trace_quantile is not None and not 0 <= int(trace_quantile) <= 99:
         raise ValueError(f"features(trace_quantile={trace_quantile}): a percentage in [0, 99]")
     ctx = ctx or default_context()
@@ -416,17 +551,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         # a single spike), then take the max over the series of a service
         k = max(1, Z.shape[0] // 20)
         top = np.sort(Z, axis=0)[-k:].mean(axis=0) if Z.shape[0] else np.zeros(Z.shape[1])
-        # series -> service, decided once per distinct label set (a TT matrix
-        # holds ~6 k series over ~50 label sets), then one scatter-max
-        memo: dict = {}
-        labs = [k[1] if len(k) > 1 else () for k in series]
-        if not all(isinstance(lb, tuple) for lb in labs):  # a caller's lists of pairs
-            labs = [lb if isinstance(lb, tuple) else tuple(tuple(kv) for kv in lb) for lb in labs]
-        by_labels = {}
-        for lb in dict.fromkeys(labs):
-            i = _series_service(("", lb), edges.services, memo)
-            by_labels[lb] = -1 if i is None else i
-        idx = np.fromiter(map(by_labels.__getitem__, labs), np.int64, len(labs))
+        # series -> service, then one scatter-max
+        idx = _labels_service(series, edges.services)
         ok = idx >= 0
         np.fmax.at(metric_score, idx[ok], np.asarray(top, np.float64)[ok])  # skips NaN
     # error rate of the calls each service serves
@@ -480,8 +606,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
                         spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
                         exemplars=ex, error_exemplars=err_ex)
-    win, ts = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps, trace_min_count,
-                             trace_quantile)
+    win, ts, mm0 = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps,
+                                  trace_min_count, trace_quantile)
     tsq = _squash(ts)  # the metric term's squashing
     params["components"]["trace"] = tsq
     params.update(trace_step_s=trace_step_s, trace_W=trace_W, trace_eps=trace_eps,
@@ -496,21 +622,73 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         params["components"]["load"] = lsq
         params["trace_load"] = True
         score = score + 0.25 * lsq
-    return Features(exp.name, edges, Z, series, score, params,
+    sc = None
+    if symptom_corr:
+        sc = _symptom_correlation(exp, ctx, win, mm0, trace_min_count, corr_min_pairs)
+        params["components"]["symptom_corr"] = sc.service
+        params["metric_corr_grid"] = sc.metric_grid
+        if sc.metric_grid == "regular":
+            params["components"]["metric_corr"] = sc.metric_service
+    return Features(exp.name, edges, Z, series, score, params, symptom_corr=sc,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
                     spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
                     edge_load=load, exemplars=ex, error_exemplars=err_ex)
 
 
-def rank(feats: Features, *, alpha: float = 0.85, iters: int = 100, tol: float = 1e-10,
+def walk_graph(edges: EdgeTable, corr: np.ndarray, rho: float = 0.2
+               ) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The correlation-weighted walk graph (the MonitorRank / MicroRCA family)
+    as a CSR (row_ptr u32, col u32 ascending per row, w f32).  With c = corr +
+    0.01, every cross-service pair i != j with count[i -> j] > 0 gives a
+    forward edge i -> j of weight c[j] — the walk moves to the callees that
+    follow the symptom — and a backward edge j -> i of weight rho * c[i];
+    weights of coinciding edges are added.  Every node i gets a self edge of
+    weight max(0, c[i] - max c[j] over its callees j), c[i] when it calls
+    nobody — the walk stays where the correlation stops rising — dropped when
+    its weight is 0."""
+    S = edges.n_services
+    c = np.asarray(corr, np.float64) + 0.01
+    if c.shape != (S,):
+        raise ValueError(f"walk_graph: corr of shape {c.shape} for {S} services")
+    if not rho >= 0:
+        raise ValueError(f"walk_graph: rho={rho} must be >= 0")
+    calls = edges.count[: S * S].reshape(S, S) > 0
+    calls[np.arange(S), np.arange(S)] = False
+    w = np.zeros((S, S))
+    has = calls | calls.T
+    w += np.where(calls, c[None, :], 0.0)              # i -> j: c[j]
+    w += np.where(calls.T, rho * c[None, :], 0.0)      # j -> i: rho * c[i]
+    for i in range(S):
+        out = np.nonzero(calls[i])[0]
+        self_w = max(0.0, c[i] - c[out].max()) if out.size else c[i]
+        if self_w > 0:
+            has[i, i] = True
+            w[i, i] = self_w
+    row_ptr = np.zeros(S + 1, np.uint32)
+    row_ptr[1:] = np.cumsum(has.sum(axis=1))
+    rows, cols = np.nonzero(has)  # row-major: ascending columns per row
+    return row_ptr, cols.astype(np.uint32), w[rows, cols].astype(np.float32)
+
+
+def rank(feats: Features, *, walk: str = "calls", rho: float = 0.2, alpha: float = 0.85,
+         iters: int = 100, tol: float = 1e-10,
          ctx: Context | None = None) -> list[tuple[str, float]]:
     """Root-cause ranking: personalized PageRank over the caller -> callee
     graph (weights = call counts), personalization = service anomaly scores
     (a non-finite score counts as 0; the uniform vector only when nothing
-    positive remains)."""
+    positive remains).  walk="correlation" (needs features(symptom_corr=True))
+    walks walk_graph(edges, symptom correlation per service, rho) instead: a
+    busy but healthy callee no longer collects walk mass for its call count."""
+    if walk not in ("calls", "correlation"):
+        raise ValueError(f"rank(walk={walk!r}): \"calls\" or \"correlation\"")
+    if walk == "correlation" and feats.symptom_corr is None:
+        raise ValueError("rank(walk=\"correlation\") needs features(symptom_corr=True)")
     ctx = ctx or default_context()
     services = feats.edges.services
-    row_ptr, col, w = feats.edges.call_graph()
+    if walk == "correlation":
+        row_ptr, col, w = walk_graph(feats.edges, feats.symptom_corr.service, rho)
+    else:
+        row_ptr, col, w = feats.edges.call_graph()
     p = np.asarray(feats.service_scores, np.float64).copy()
     p = np.where(np.isfinite(p), p, 0.0)
     if p.sum() <= 0:

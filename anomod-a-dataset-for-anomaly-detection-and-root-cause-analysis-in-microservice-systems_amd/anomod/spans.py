@@ -324,6 +324,19 @@ class EdgeWindows:
         ts = (self.t0_us + np.arange(T, dtype=np.float64) * self.step_us) / 1e6
         return MetricMatrix(X, ts, series)
 
+    def symptom(self, min_count: int = 5) -> np.ndarray:
+        """The front-door latency series, f32 [T]: per window log2(1 + sum of
+        sum_us / sum of count) over the ROOT rows (parent index S: the spans
+        that entered the system), computed in f64; NaN where the window holds
+        fewer than max(min_count, 1) such spans."""
+        S = len(self.services)
+        cnt = self.count[:, S * S:S * S + S].sum(axis=1)
+        tot = self.sum_us[:, S * S:S * S + S].sum(axis=1).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            y = np.where(cnt >= max(int(min_count), 1),
+                         np.log2(1.0 + tot / cnt.astype(np.float64)), np.nan)
+        return y.astype(np.float32)
+
 
 @dataclass
 class EdgeLoad:

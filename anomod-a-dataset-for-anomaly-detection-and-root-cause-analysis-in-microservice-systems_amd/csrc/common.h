@@ -42,7 +42,8 @@ enum Stage { kStageEdgeAgg = 0, kStageEdgeFinal = 1, kStageEdgeReduce = 2, kStag
              kStagePagerank = 4, kStageTraceStruct = 5, kStageSegments = 6, kStageSummary = 7,
              kStageGroup = 8, kStageEdgeWindows = 9, kStageEdgeWindowKernel = 10,
              kStageEdgeLoad = 11, kStageEdgeLoadKernel = 12, kStageEdgeLoadScan = 13,
-             kStageEdgeExemplars = 14, kStageEdgeExemplarsKernel = 15, kNumStages = 16 };
+             kStageEdgeExemplars = 14, kStageEdgeExemplarsKernel = 15, kStageSeriesCorr = 16,
+             kNumStages = 17 };
 
 // Host wall-clock slots (anomod_ctx_host_ms): the last occurrence of each
 // one-off setup step, or of a call phase the stage events cannot see.

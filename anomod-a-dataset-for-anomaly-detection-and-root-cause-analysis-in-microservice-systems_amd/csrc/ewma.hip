@@ -42,19 +42,8 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "series.h"
 #include "synth.h"
-
-struct anomod_series {
-  int device = 0;
-  uint64_t T = 0, S = 0;
-  float* X = nullptr;      // [T][S] rows or [ceil(T/16)][S][16] tiles (sized for the tiles)
-  bool tiled = false;
-  float* Z = nullptr;      // [T/W][S] (allocated lazily for the largest W seen)
-  size_t z_cap = 0;
-  double* m = nullptr;     // [S]
-  double* v = nullptr;     // [S]
-  uint32_t* n = nullptr;   // [S] valid samples seen
-};
 
 namespace anomod {
 namespace {
@@ -166,29 +155,7 @@ __global__ __launch_bounds__(64) void ewma_z_kernel(const float* __restrict__ X,
 // Sequential recurrence over the tiled layout.  kTiles tiles (16 steps each)
 // per load block, two blocks in flight; blocks wholly inside T run without
 // per-step bounds checks.
-#ifndef ANOMOD_EWMA_TILE
-#define ANOMOD_EWMA_TILE 16
-#endif
-constexpr int kTile = ANOMOD_EWMA_TILE;  // steps per tile (one lane's contiguous run)
-static_assert(kTile % 16 == 0 && 64 % kTile == 0, "tile steps");
-#ifndef ANOMOD_EWMA_QMAJOR
-#define ANOMOD_EWMA_QMAJOR 1
-#endif
-// Float index of steps 4q .. 4q+3 of series s in tile `tile` (a tile holds
-// kTile steps of every series: S * kTile floats).  q-major (default): the
-// float4 groups of one q for all series contiguous, so a wave's load
-// instruction reads 1 KiB contiguously; series-major (ANOMOD_EWMA_QMAJOR=0,
-// the r01/r02 layout): each series' kTile steps contiguous.
-__host__ __device__ __forceinline__ uint64_t tile_off(uint64_t tile, uint64_t S, uint64_t s,
-                                                      uint64_t q) {
-  if constexpr (ANOMOD_EWMA_QMAJOR) return tile * S * kTile + (q * S + s) * 4;
-  else return (tile * S + s) * kTile + 4 * q;
-}
-#ifndef ANOMOD_ZT_TILES
-#define ANOMOD_ZT_TILES 4
-#endif
-constexpr int kZtTiles = ANOMOD_ZT_TILES;  // tiles per load block (two blocks in flight)
-constexpr int kPadTiles = 2 * kZtTiles;  // slack tiles past ceil(T/16) read by the prefetch
+// (the tile geometry, tile_off and the prefetch slack are in series.h)
 
 // kChk: steps between window-end checks in dense blocks — 4 when W % 4 == 0
 // (every window then ends on a float4 boundary: the window position starts at

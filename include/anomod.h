@@ -125,7 +125,8 @@ int anomod_ctx_synchronize(anomod_ctx* ctx);
  * 11 = edge-load pass (keys form: per-span edge keys; the stream kernel; the
  *      scan), 12 = its stream kernel alone, 13 = its scan alone,
  * 14 = edge-exemplars pass (keys form: per-span edge keys; the stream kernel;
- *      the gather), 15 = its stream kernel alone.                           */
+ *      the gather), 15 = its stream kernel alone,
+ * 16 = series-correlation kernel.                                           */
 int anomod_ctx_stage_ms(const anomod_ctx* ctx, int stage, double* ms);
 /* Host wall milliseconds of the last occurrence of a one-off setup step or of
  * a call phase the stage events above cannot see, and how many times it
@@ -886,6 +887,45 @@ int anomod_series_download(anomod_ctx* ctx, const anomod_series* ser, float* X);
 int anomod_series_ewma_z(anomod_ctx* ctx, anomod_series* ser, float alpha, uint32_t W,
                          float eps, float* Z_host /* may be NULL */);
 int anomod_series_free(anomod_series* ser);
+
+/* ---- series correlation ---------------------------------------------------
+ * Pearson correlation of every column of X[T][S] (f32) against K target
+ * columns Y[T][K] (host, row-major, f32), pairwise-complete over missing
+ * samples, in one pass over X.
+ *  - Pair set.  Step t is a pair of (k, s) iff X[t][s] and Y[t][k] are both
+ *    finite; NaN and +-inf are missing.  n[k][s] is the size of that set.
+ *  - Pivots.  px_s is the first finite X[t][s] of the call, whatever Y holds;
+ *    py_k is the first finite Y[t][k].
+ *  - Sums.  Over the pair set, in f64 and in step order: sum x', sum y',
+ *    sum x'^2, sum y'^2, sum x'y' with x' = (double)x - px, y' = (double)y - py.
+ *    sxx = sum x'^2 - (sum x')^2 / n, syy likewise,
+ *    sxy = sum x'y' - sum x' sum y' / n.
+ *  - Result.  r[k][s] = NaN when n < max(min_pairs, 2) or sxx <= 0 or
+ *    syy <= 0 (a constant series: x' is exactly 0); otherwise
+ *    sxy / sqrt(sxx * syy) clamped to [-1, 1].  A series with no finite
+ *    sample gives n = 0, r = NaN.
+ *  - Samples are |x| <= 2^62 or missing, as for EWMA.
+ *  - Accuracy: |r - r_exact| <= 8 T 2^-53 max(kx, ky) + 2^-50 with
+ *    kx = sum (x - px)^2 / sum (x - mean)^2 over the pair set, ky likewise
+ *    (derivation in csrc/series_corr.hip).
+ *  - K == 0, K > ANOMOD_CORR_MAX_TARGETS, a NULL ser / X / Y / r or T >= 2^32
+ *    is ANOMOD_EINVAL; T == 0 or S == 0 is ANOMOD_OK with nothing written.
+ *    n may be NULL.
+ *  - The call reads the resident matrix in the layout it has (tiles or rows),
+ *    re-lays nothing, leaves the EWMA state (m, v, n) alone: a later
+ *    anomod_series_ewma_z gives the bits it would have given without it.
+ *  - The same input gives the same bits from run to run and from either
+ *    layout; the order of summation depends on T and S only.
+ * Stage 16 of anomod_ctx_stage_ms times the kernel.                         */
+#define ANOMOD_CORR_MAX_TARGETS 8
+int anomod_series_correlate(anomod_ctx* ctx, const anomod_series* ser,
+                            const float* Y /* host, row-major [T][K] */, uint32_t K,
+                            uint32_t min_pairs, double* r /* [K][S] */,
+                            uint32_t* n /* [K][S], may be NULL */);
+/* Host convenience, as anomod_ewma_z is to anomod_series_ewma_z: X is host
+ * rows [T][S], uploaded for the one call (it must fit the device).          */
+int anomod_correlate(anomod_ctx* ctx, const float* X, uint64_t T, uint64_t S, const float* Y,
+                     uint32_t K, uint32_t min_pairs, double* r, uint32_t* n);
 
 /* ---- personalized PageRank RCA -----------------------
  * networkx 3.4.2 pagerank convention: out-edge CSR (row = caller) with
