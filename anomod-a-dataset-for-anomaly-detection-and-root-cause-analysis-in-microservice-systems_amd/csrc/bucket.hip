@@ -761,7 +761,12 @@ __device__ void bucket_huge(unsigned char* lds, uint32_t c, uint32_t a0, uint32_
   __syncthreads();
   const uint32_t d = hm[0];
   if (hm[1] || d > kHugeKeys) {
-    if (tid == 0) atomicAdd(too_big, 1ull);
+    // (dcnt[c] = 0: the trace_ptr kernels still run over every bucket before
+    // the host reads too_big, and nothing else ever writes this entry)
+    if (tid == 0) {
+      atomicAdd(too_big, 1ull);
+      dcnt[c] = 0u;
+    }
     return;
   }
   for (uint32_t i = tid; i < kHugeSlots; i += W)
@@ -1092,15 +1097,21 @@ __device__ void bucket_sort_one(BucketLds<W, PER>& L, uint32_t c, uint64_t* __re
     if (small) {
       if (tid == 0) {
         const unsigned long long i = atomicAdd(over_n, 1ull);
-        if (i < over_cap) over[i] = c;
-        else atomicAdd(too_big, 1ull);
+        if (i < over_cap) {
+          over[i] = c;
+        } else {  // (a bucket nobody sorts: no traces counted, as in bucket_huge)
+          atomicAdd(too_big, 1ull);
+          dcnt[c] = 0u;
+        }
       }
       return;
     }
-    if constexpr (sizeof(BucketLds<W, PER>) >= 81920 + 16 + 4 * (W / kWv))
+    if constexpr (sizeof(BucketLds<W, PER>) >= 81920 + 16 + 4 * (W / kWv)) {
       bucket_huge<W>(reinterpret_cast<unsigned char*>(&L), c, a0, m, pin, rec, out, dcnt, too_big);
-    else if (tid == 0)
+    } else if (tid == 0) {
       atomicAdd(too_big, 1ull);
+      dcnt[c] = 0u;
+    }
     return;
   }
   if (m == 0) {

@@ -647,7 +647,9 @@ int ensure_group_ws(anomod_ctx* ctx, uint64_t n, bool both_records) {
   ws->tile_cap = tiles + 2048;
   const size_t tcnt_words = std::max<size_t>(tiles * kDig, ws->tile_cap * 2048);
   ws->tcnt_words = tcnt_words;
-  const size_t bsum_words = (tiles / kTScanRows + 2) * 2048;
+  // (the bucket path's level-A tiles hold 2048 records, half of kSTile: twice
+  // as many scan blocks, each with up to 2048 digit sums)
+  const size_t bsum_words = (2 * tiles / kTScanRows + 2) * 2048;
   // Bytes per span: 32 (the level-A record buffer) + 16 (two pair buffers;
   // the LSD path's 2-B digits live in the second, which only the bucket path
   // uses) + 8 (trace_ptr, or the join's edge records) + ~2 (tile counts,

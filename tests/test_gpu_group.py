@@ -8,6 +8,7 @@ import pytest
 import anomod
 from oracle import native, spec
 
+from group_ref import unmix64 as _unmix64
 from test_gpu_edge import _random_spanset, assert_table_equal
 
 pytestmark = pytest.mark.gpu
@@ -77,23 +78,6 @@ def test_group_empty(ctx):
     assert g.n_spans == 0 and g.n_traces == 0
     t = ctx.edge_aggregate(dev)
     assert t.count.sum() == 0
-
-
-def _unmix64(k: np.ndarray) -> np.ndarray:
-    """Inverse of spec.mix64 (hashes with chosen mixed keys)."""
-    M = 2**64
-
-    def unxorshift(y, s):
-        x = y.copy()
-        for _ in range(64 // s + 1):
-            x = y ^ (x >> np.uint64(s))
-        return x
-
-    z = unxorshift(np.asarray(k, np.uint64), 31)
-    z = z * np.uint64(pow(0x94D049BB133111EB, -1, M))
-    z = unxorshift(z, 27)
-    z = z * np.uint64(pow(0xBF58476D1CE4E5B9, -1, M))
-    return unxorshift(z, 30)
 
 
 def test_mixed_buckets_and_pass_retry(ctx):
