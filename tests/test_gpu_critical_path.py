@@ -124,7 +124,9 @@ def test_device_generated_set(ctx):
 
 # ------------------------------------------------------------------ hand-built shapes
 def test_sixty_five_one_span_traces(ctx):
-    """Crosses the chunk's 64-trace limit; every span is a head."""
+    """More one-span traces than a chunk's 64; every span is a head.  (The
+    share policy packs only the last 16 of them into one chunk: the 64-trace
+    limit itself is met in test_gpu_walk_borders.py.)"""
     n = 65
     sp = _spanset(3, [1] * n, np.arange(1, n + 1), np.zeros(n), np.arange(n) * 3)
     sp = _with_start(sp, T0_US + np.arange(n) * 10)
@@ -136,7 +138,8 @@ def test_sixty_five_one_span_traces(ctx):
 @pytest.mark.parametrize("L_", [256, 257])
 def test_trace_at_the_chunk_limit(ctx, L_, monkeypatch, capfd):
     """The same random tree with random starts at 256 (one chunk) and 257
-    spans (long-trace kernel), between short traces."""
+    spans (long-trace kernel), between short traces (each of the three a chunk
+    of its own: no dynamic tail, nothing is packed)."""
     monkeypatch.setenv("ANOMOD_LOG_KERNEL", "1")
     sp = _random_tree(np.random.default_rng(31), [3, L_, 3], dur_hi=5000)
     sp = random_starts(sp, seed=4)

@@ -55,7 +55,9 @@ def test_hand_made_trace(ctx):
 
 
 def test_sixty_five_one_span_traces(ctx):
-    """Crosses the chunk's 64-trace limit; every span starts and ends its failure."""
+    """More one-span traces than a chunk's 64; every span starts and ends its
+    failure.  (The share policy packs only the last 16 of them into one chunk:
+    the 64-trace limit itself is met in test_gpu_walk_borders.py.)"""
     n = 65
     sp = build(3, [([t + 1], [0], [ERR], [t % 3]) for t in range(n)])
     got = _check(ctx, sp)

@@ -150,7 +150,10 @@ def test_device_grouped_set(ctx):
 
 # ------------------------------------------------------------------ hand-built shapes
 def test_sixty_five_one_span_traces(ctx):
-    """Crosses the chunk's 64-trace limit."""
+    """More one-span traces than a chunk's 64 — but the share policy walks the
+    first 49 as chunks of their own and packs only the last 16 (65 // 4), so
+    the 64-trace limit is not met here: test_gpu_walk_borders.py (pack_64x4,
+    pack_65x4, pack_span_limit) closes chunks by it."""
     n = 65
     sp = _spanset(3, [1] * n, np.arange(1, n + 1), np.zeros(n), np.arange(n) * 3)
     got, su = _check(ctx, sp)
@@ -160,7 +163,10 @@ def test_sixty_five_one_span_traces(ctx):
 @pytest.mark.parametrize("L_", [256, 257])
 def test_trace_at_the_chunk_limit(ctx, L_):
     """A chain trace of exactly 256 (one chunk) / 257 spans (long-trace
-    kernel) between short traces."""
+    kernel) between short traces.  With three traces there is no dynamic tail
+    (3 // 4 == 0): every trace is a chunk of its own, so this is about the
+    trace's length, not about packing (253 + 3 against 254 + 3 is
+    pack_span_limit in test_gpu_walk_borders.py)."""
     sid = np.arange(1, L_ + 7, dtype=np.uint64) + np.uint64(1 << 33)
     lens = [3, L_, 3]
     pid = np.r_[np.uint64(0), sid[:-1]]

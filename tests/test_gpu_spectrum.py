@@ -118,7 +118,10 @@ def test_long_topology_and_hand_made_long_traces(ctx, monkeypatch, capfd):
 # ------------------------------------------------------------------ chunk edges
 def test_chunk_edges(ctx):
     """Traces of 1 / 255 / 256 / 257 spans, an empty trace, 65 single-span
-    traces in a row (a chunk holds 64), and 200 spans on one edge."""
+    traces in a row, and 200 spans on one edge.  Of the 74 traces only the last
+    18 (217 spans) are packed, into one chunk; every other trace is a chunk of
+    its own, so no chunk closes at 64 traces or 256 spans here — those borders
+    are test_gpu_walk_borders.py's."""
     rng = np.random.default_rng(7)
     S = 5
     lens = np.r_[[1, 255, 256, 257, 0], [1] * 65, [200], [0, 3, 0]]

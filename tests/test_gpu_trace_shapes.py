@@ -147,7 +147,9 @@ def test_device_generated_set(ctx):
 
 # ------------------------------------------------------------------ hand-built shapes
 def test_sixty_five_one_span_traces(ctx):
-    """Crosses the chunk's 64-trace limit; every span is a head."""
+    """More one-span traces than a chunk's 64; every span is a head.  (The
+    share policy packs only the last 16 of them into one chunk: the 64-trace
+    limit itself is met in test_gpu_walk_borders.py.)"""
     n = 65
     sp = spanset(3, [1] * n, np.arange(1, n + 1), np.zeros(n))
     got = _check(ctx, sp)
@@ -160,7 +162,8 @@ def test_sixty_five_one_span_traces(ctx):
 def test_trace_at_the_chunk_limit(ctx, L_, kind, monkeypatch, capfd):
     """A random tree and a pure chain at 256 (one chunk, all 8 rounds for the
     chain) and at 257 spans (long-trace kernel, 9 rounds), between short
-    traces."""
+    traces (each of the three a chunk of its own: no dynamic tail, nothing is
+    packed)."""
     monkeypatch.setenv("ANOMOD_LOG_KERNEL", "1")
     if kind == "tree":
         sp = random_tree(np.random.default_rng(31), [3, L_, 3], self_ref=0.01)

@@ -190,15 +190,16 @@ def big_slot(ids) -> np.ndarray:
     return ((h >> np.uint64(64 - 13)) & np.uint64(BIG_SLOTS - 1)).astype(np.int64)
 
 
-def tail_chunks(lens) -> list:
+def tail_chunks(lens, start=None) -> list:
     """(first trace, k, n) of every chunk the device forms over the dynamic
-    tail of a set with these trace lengths: the last nt // 2 traces in
+    tail of a set with these trace lengths: the last nt // 2 traces (or, for
+    another driver of the same chunk walk, the traces from `start` on) in
     segments of DYN_SEG, each walked from its start in chunks of the most
     leading traces (up to CHUNK_TRACES) that hold <= STAGE spans together
     (chunk.h make_chunk); k = 0 is a trace longer than STAGE on its own."""
     nt = len(lens)
     out = []
-    for s in range(nt - nt // 2, nt, DYN_SEG):
+    for s in range(nt - nt // 2 if start is None else start, nt, DYN_SEG):
         e, t = min(s + DYN_SEG, nt), s
         while t < e:
             k = n = 0
