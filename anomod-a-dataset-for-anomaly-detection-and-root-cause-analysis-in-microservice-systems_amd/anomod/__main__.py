@@ -1,6 +1,7 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
                                  [--spectrum] [--critical-path] [--shapes]
-                                 [--error-origins] [--trace-step S [--trace-load]]
+                                 [--error-origins] [--repeats]
+                                 [--trace-step S [--trace-load]]
                                  [--exemplars K]
                                  [--trace-step S --symptom-corr [--walk correlation]]
                                  [--baseline <trace file|dir>]
@@ -57,6 +58,21 @@ def error_origins_doc(eo) -> dict:
             "services": {s: {"origin": int(org[i]), "propagated": int(prop[i]),
                              "surfaced": int(surf[i]), "mean_hops": float(hops[i])}
                          for i, s in enumerate(eo.services)}}
+
+
+def call_repeats_doc(rep) -> dict:
+    """The "call_repeats" object of the features JSON: per callee service the
+    logical calls (groups), the calls beyond the first of a group (repeats),
+    the groups that repeated around a failure (retried = recovered +
+    exhausted), the members that started after a failure of their group had
+    ended (after_error; 0 without start times: `timed`) and the largest
+    group."""
+    cols = {k: rep.per_service(k) for k in ("groups", "repeats", "retried", "recovered",
+                                            "exhausted", "after_error", "size_max")}
+    return {"timed": bool(rep.timed), "grouped_spans": int(rep.grouped_spans),
+            "max_size": int(rep.max_size),
+            "services": {s: {k: int(v[i]) for k, v in cols.items()}
+                         for i, s in enumerate(rep.services)}}
 
 
 def edge_load_doc(load) -> dict:
@@ -177,6 +193,11 @@ def main(argv=None) -> int:
                    help="also tell the error-flagged spans whose failure started there from "
                         "those that relayed a callee's failure, score services by the failures "
                         "that started in them, and write the counts as \"error_origins\"")
+    f.add_argument("--repeats", action="store_true",
+                   help="also count, per edge, how often one parent span called the same "
+                        "callee more than once (retries, retry storms, N+1 loops), score the "
+                        "growth of that amplification against --baseline, and write the "
+                        "counts as \"call_repeats\"")
     f.add_argument("--exemplars", type=int, metavar="K",
                    help="also list, for each of the top 5 ranked services, the K slowest calls "
                         "of its slowest incoming edge and the K slowest failed calls of its "
@@ -213,13 +234,13 @@ def main(argv=None) -> int:
     if args.baseline:
         baseline = features(load_experiment(args.baseline), W=args.window,
                             self_time=args.self_time, critical_path=args.critical_path,
-                            shapes=args.shapes)
+                            shapes=args.shapes, repeats=args.repeats)
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
                      critical_path=args.critical_path, trace_quantile=args.trace_quantile,
                      shapes=args.shapes, error_origins=args.error_origins,
                      trace_load=args.trace_load, exemplars=args.exemplars,
-                     symptom_corr=args.symptom_corr)
+                     symptom_corr=args.symptom_corr, repeats=args.repeats)
     ranking = rank(feats, walk=args.walk, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -256,6 +277,8 @@ def main(argv=None) -> int:
     if feats.error_origins is not None:
         doc["error_origins"] = error_origins_doc(feats.error_origins)
         doc["loop_spans"] = int(feats.error_origins.loop_spans)
+    if feats.repeats is not None:
+        doc["call_repeats"] = call_repeats_doc(feats.repeats)
     if feats.edge_load is not None:
         doc["edge_load"] = edge_load_doc(feats.edge_load)
         doc["load_scores"] = dict(zip(feats.edges.services,

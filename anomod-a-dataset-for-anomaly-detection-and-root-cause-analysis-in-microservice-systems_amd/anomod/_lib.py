@@ -19,6 +19,7 @@ HIST_SUB_BITS = 5
 HIST_BINS = 896
 ROOT_ROWS = 2
 FLAG_ERROR = 0x1
+REPEAT_BINS = 8
 CORR_MAX_TARGETS = 8
 UNIQUE_ID_BYTES = 128
 TOPO_SN = 0
@@ -178,6 +179,26 @@ class ErrorOriginsC(C.Structure):
     ]
 
 
+class CallRepeatsC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("max_size", C.c_uint32),
+        ("timed", C.c_uint32),
+        ("grouped_spans", C.c_uint64),
+        ("groups", C.POINTER(C.c_uint64)),
+        ("repeats", C.POINTER(C.c_uint64)),
+        ("repeated", C.POINTER(C.c_uint64)),
+        ("retried", C.POINTER(C.c_uint64)),
+        ("recovered", C.POINTER(C.c_uint64)),
+        ("exhausted", C.POINTER(C.c_uint64)),
+        ("after_error", C.POINTER(C.c_uint64)),
+        ("size_hist", C.POINTER(C.c_uint64)),
+        ("size_max", C.POINTER(C.c_uint32)),
+        ("span_group_size", C.POINTER(C.c_uint32)),
+        ("span_after_error", C.POINTER(C.c_uint8)),
+    ]
+
+
 class TraceStructC(C.Structure):
     _fields_ = [
         ("n_services", C.c_uint32),
@@ -301,6 +322,7 @@ _SIGS = {
     "anomod_trace_spectrum_spans": (_i32, [_vp, _vp, _P(TraceSpectrumC)]),
     "anomod_trace_shapes_spans": (_i32, [_vp, _vp, _P(TraceShapesC)]),
     "anomod_error_origins_spans": (_i32, [_vp, _vp, _P(ErrorOriginsC)]),
+    "anomod_call_repeats_spans": (_i32, [_vp, _vp, _P(CallRepeatsC)]),
     "anomod_edge_aggregate_host": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _u32, _i32,
                                           _P(_i32), _P(_i32), _P(EdgeTableC)]),
     "anomod_edge_aggregate": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _P(EdgeTableC)]),

@@ -11,8 +11,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import (CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes,
-                    TraceSpectrum, TraceStructure, edge_rows)
+from .spans import (CallRepeats, CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
+                    TraceShapes, TraceSpectrum, TraceStructure, edge_rows)
 
 
 @dataclass
@@ -711,6 +711,34 @@ class Context:
                                                              C.byref(cs)))
             eo.error_spans, eo.loop_spans = int(cs.error_spans), int(cs.loop_spans)
             return eo
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def call_repeats(self, spans: DeviceSpans | SpanSet, per_span: bool = False) -> CallRepeats:
+        """Call repeats of a grouped set (anomod_call_repeats_spans): per edge
+        row the groups — one parent span's calls to one callee service — the
+        calls beyond the first of a group, the groups that repeated, those
+        that repeated around a failure (retried = recovered + exhausted), the
+        group-size histogram and maximum, and, for a set with start times, the
+        members that started after a failure of their group had ended.
+        per_span=True also returns span_group_size and span_after_error by
+        span position.  Rank-local.  A host set is uploaded for the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            tmp = spans = self.upload(spans)
+        try:
+            cr = CallRepeats.empty(spans.services, int(spans.n_spans) if per_span else None)
+            cs = L.CallRepeatsC(len(spans.services), 0, 0, 0,
+                                *(L.ptr(getattr(cr, k), C.c_uint64) for k in cr.TABLES[:8]),
+                                L.ptr(cr.size_max, C.c_uint32),
+                                L.ptr(cr.span_group_size, C.c_uint32),
+                                L.ptr(cr.span_after_error, C.c_uint8))
+            self._check(self._lib.anomod_call_repeats_spans(self.handle, spans.handle,
+                                                            C.byref(cs)))
+            cr.grouped_spans, cr.max_size = int(cs.grouped_spans), int(cs.max_size)
+            cr.timed = bool(cs.timed)
+            return cr
         finally:
             if tmp is not None:
                 tmp.free()

@@ -26,8 +26,8 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import (EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet, TraceShapes, TraceSpectrum,
-                    edge_rows, spectrum_thresholds)
+from .spans import (CallRepeats, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
+                    TraceShapes, TraceSpectrum, edge_rows, spectrum_thresholds)
 
 # --------------------------------------------------------------------------
 # Ground-truth labels (experiment name -> faulty service), SURVEY.md §2:
@@ -214,6 +214,8 @@ class Features:
     shapes: TraceShapes | None = None
     # features(error_origins=True): where failures started and how far they travelled
     error_origins: ErrorOrigins | None = None
+    # features(repeats=True): repeated and retried calls per edge
+    repeats: CallRepeats | None = None
     # features(trace_load=True): per-window busy time and carried calls of every edge
     edge_load: EdgeLoad | None = None
     # features(exemplars=K): the K slowest calls of every edge, and the K
@@ -280,6 +282,40 @@ def _latency_shift(cur: EdgeTable, base: EdgeTable, min_count: int = 10) -> np.n
     ratio = np.zeros(cur.count.shape[0])
     ratio[ok] = np.maximum(0.0, np.log2(cur.p99_us[ok] / bp[ok]))
     return ratio.reshape(S + 2, S).max(axis=0)
+
+
+def _repeat_components(rep: CallRepeats, min_groups: int = 10) -> tuple[np.ndarray, np.ndarray]:
+    """Per service (amplification, retry_rate): over the incoming rows with >=
+    min_groups groups the largest row amplification minus 1 (0 without such a
+    row), and retried / groups, both summed over the incoming rows (0 where
+    the service has no group)."""
+    S = len(rep.services)
+    amp = np.where(rep.groups >= min_groups, rep.amplification() - 1.0, 0.0)
+    g = rep.per_service("groups").astype(np.float64)
+    rate = np.divide(rep.per_service("retried").astype(np.float64), g, out=np.zeros(S),
+                     where=g > 0)
+    return amp.reshape(S + 2, S).max(axis=0), rate
+
+
+def _repeat_shift(cur: CallRepeats, base: CallRepeats, min_groups: int = 10) -> np.ndarray:
+    """Per service: largest log2 growth of an incoming edge's call
+    amplification over the same edge — matched by service NAMES, as
+    _latency_shift matches them — in a baseline run (rows with >= min_groups
+    groups on both sides); never below 0."""
+    S, Sb = len(cur.services), len(base.services)
+    pos = {s: i for i, s in enumerate(base.services)}
+    m = np.array([pos.get(s, -1) for s in cur.services] + [Sb, Sb + 1], np.int64)  # + ROOT, ORPHAN
+    p_cur = np.repeat(np.arange(S + 2), S)
+    c_cur = np.tile(np.arange(S), S + 2)
+    pb, cb = m[p_cur], m[c_cur]
+    have = (pb >= 0) & (cb >= 0)
+    rows = np.where(have, pb * Sb + np.where(cb >= 0, cb, 0), 0)
+    bg = np.where(have, base.groups[rows], 0)
+    ba = base.amplification()[rows]
+    ok = have & (cur.groups >= min_groups) & (bg >= min_groups)
+    shift = np.zeros(cur.groups.shape[0])
+    shift[ok] = np.maximum(0.0, np.log2(cur.amplification()[ok] / ba[ok]))
+    return shift.reshape(S + 2, S).max(axis=0)
 
 
 def _squash(x: np.ndarray) -> np.ndarray:
@@ -463,7 +499,7 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              trace_quantile: int | None = None, shapes: bool = False,
              error_origins: bool = False, trace_load: bool = False,
              exemplars: int | None = None, symptom_corr: bool = False,
-             corr_min_pairs: int = 3) -> Features:
+             corr_min_pairs: int = 3, repeats: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -523,6 +559,15 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     (components["metric_corr"]).  Features.symptom_corr holds both with the
     per-column r and n; rank(walk="correlation") walks by them.  No score or
     other component changes.
+    With repeats the result also holds the call repeats (Context.call_repeats:
+    how often one parent span called the same callee more than once) with
+    components["amplification"] — per service, over the incoming edge rows
+    with >= 10 groups, the largest spans-per-logical-call minus 1 — and
+    components["retry_rate"] — retried / groups over the incoming rows.
+    Against a baseline that has repeats the score gains 0.25 * the squashed
+    components["repeat_shift"]: the largest log2 growth of an incoming row's
+    amplification over the same row of the baseline (rows matched by service
+    names, >= 10 groups on both sides); without a baseline no score changes.
     Non-finite window scores: a column whose score is NaN is skipped, +inf
     squashes to 1, so service_scores stays finite."""
     if trace_load and trace_step_s is None:
@@ -598,14 +643,26 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
             nov = census.novelty(exp.spans, baseline.shapes)
             params["components"]["shape_novelty"] = nov
             score = score + 0.25 * nov
+    rep_table, rep_term = None, None
+    if repeats:
+        rep_table = ctx.call_repeats(exp.spans)
+        amp, retry_rate = _repeat_components(rep_table)
+        params["components"]["amplification"] = amp
+        params["components"]["retry_rate"] = retry_rate
+        if baseline is not None and baseline.repeats is not None:
+            shift = _repeat_shift(rep_table, baseline.repeats)
+            params["components"]["repeat_shift"] = shift
+            rep_term = 0.25 * _squash(shift)   # added last: the other terms sum as without it
     ex = err_ex = None
     if exemplars is not None:
         ex = ctx.edge_exemplars(exp.spans, int(exemplars))
         err_ex = ctx.edge_exemplars(exp.spans, int(exemplars), errors_only=True)
     if trace_step_s is None:
+        if rep_term is not None:
+            score = score + rep_term
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
                         spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
-                        exemplars=ex, error_exemplars=err_ex)
+                        exemplars=ex, error_exemplars=err_ex, repeats=rep_table)
     win, ts, mm0 = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps,
                                   trace_min_count, trace_quantile)
     tsq = _squash(ts)  # the metric term's squashing
@@ -629,10 +686,12 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         params["metric_corr_grid"] = sc.metric_grid
         if sc.metric_grid == "regular":
             params["components"]["metric_corr"] = sc.metric_service
+    if rep_term is not None:
+        score = score + rep_term
     return Features(exp.name, edges, Z, series, score, params, symptom_corr=sc,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
                     spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
-                    edge_load=load, exemplars=ex, error_exemplars=err_ex)
+                    edge_load=load, exemplars=ex, error_exemplars=err_ex, repeats=rep_table)
 
 
 def walk_graph(edges: EdgeTable, corr: np.ndarray, rho: float = 0.2

@@ -647,6 +647,61 @@ class ErrorOrigins:
                          where=org > 0)
 
 
+@dataclass
+class CallRepeats:
+    """Call repeats of a span set (anomod_call_repeats_spans): a group is one
+    parent span's calls to one callee service, n its size and e its
+    error-flagged members.  The edge table counts spans; groups counts the
+    logical calls behind them, repeats the calls beyond the first of a group.
+    Rows as in EdgeTable; only the first S * S rows hold groups (a head has no
+    parent), and groups + repeats there equals EdgeTable.count for a set
+    without a self-referencing span."""
+
+    services: list[str]
+    groups: np.ndarray                # u64 [E] groups (logical calls)
+    repeats: np.ndarray               # u64 [E] sum of n - 1
+    repeated: np.ndarray              # u64 [E] groups with n >= 2
+    retried: np.ndarray               # u64 [E] ... and e >= 1
+    recovered: np.ndarray             # u64 [E] ... and 1 <= e < n
+    exhausted: np.ndarray             # u64 [E] ... and e == n
+    after_error: np.ndarray           # u64 [E] members that started after a failure of their group ended
+    size_hist: np.ndarray             # u64 [E, REPEAT_BINS] groups by min(floor(log2 n), 7)
+    size_max: np.ndarray              # u32 [E] largest n (0 for a row without a group)
+    grouped_spans: int = 0            # spans that have a parent
+    max_size: int = 0                 # the largest group of the set
+    timed: bool = False               # the set has start times (else after_error is all zero)
+    span_group_size: np.ndarray | None = None   # u32 [n_spans] (per_span=True)
+    span_after_error: np.ndarray | None = None  # u8 [n_spans] (per_span=True)
+
+    TABLES = ("groups", "repeats", "repeated", "retried", "recovered", "exhausted", "after_error",
+              "size_hist", "size_max")
+
+    @staticmethod
+    def empty(services: list[str], n_spans: int | None = None) -> "CallRepeats":
+        """Zeroed tables over `services`; n_spans: also the per-span columns."""
+        E = edge_rows(len(services))
+        return CallRepeats(list(services), *(np.zeros(E, np.uint64) for _ in range(7)),
+                           np.zeros((E, L.REPEAT_BINS), np.uint64), np.zeros(E, np.uint32), 0, 0,
+                           False,
+                           None if n_spans is None else np.zeros(n_spans, np.uint32),
+                           None if n_spans is None else np.zeros(n_spans, np.uint8))
+
+    def per_service(self, name: str) -> np.ndarray:
+        """A table summed over the parent rows: one value per callee service
+        (the maximum for size_max; [S, REPEAT_BINS] for size_hist)."""
+        S = len(self.services)
+        t = getattr(self, name)
+        t = t.reshape((S + 2, S) + t.shape[1:])
+        return t.max(axis=0) if name == "size_max" else t.sum(axis=0)
+
+    def amplification(self) -> np.ndarray:
+        """Per edge row: spans per logical call, (groups + repeats) / groups;
+        1 where the row has no group."""
+        g = self.groups.astype(np.float64)
+        return np.divide(g + self.repeats.astype(np.float64), g, out=np.ones(g.shape[0]),
+                         where=g > 0)
+
+
 def spectrum_thresholds(base: EdgeTable, services: list[str], *, rows: str = "root",
                         min_count: int = 10) -> np.ndarray:
     """Latency thresholds (u32 [E] over `services`) for Context.trace_spectrum

@@ -745,6 +745,73 @@ typedef struct {
 } anomod_error_origins;
 int anomod_error_origins_spans(anomod_ctx* ctx, const anomod_spans* spans,
                                anomod_error_origins* out);
+/* Call repeats of a grouped set: how often one parent span called the same
+ * callee service more than once — a retry after a failure, a retry storm, an
+ * N+1 loop over a result set.  The edge table counts every span once; this
+ * call says how many logical calls they were.  With err(i) = flags[i] &
+ * ANOMOD_FLAG_ERROR and par(i) the parent rule of the self-time call (a ROOT,
+ * an ORPHAN and a SELF reference have no parent and are heads; duplicated ids
+ * resolve to the first carrier), a span with a parent belongs to the group
+ *   G(j, c) = { i : par(i) = j, svc[i] = c }
+ * — one parent span's calls to one callee service; heads belong to no group.
+ * All members of a group share the edge row r = svc[j] * S + c, one of the
+ * first S * S rows of anomod_edge_aggregate_spans.  With n the size of a
+ * group and e its error-flagged members, per edge row over the groups of the
+ * row:
+ *   groups      the groups (the logical calls)
+ *   repeats     sum of n - 1
+ *   repeated    groups with n >= 2
+ *   retried     groups with n >= 2 and e >= 1
+ *   recovered   groups with n >= 2 and 1 <= e < n (some attempt went through)
+ *   exhausted   groups with n >= 2 and e == n
+ *   size_max    the largest n (0 for a row without a group)
+ *   size_hist   [row][b] groups by b = min(floor(log2 n), ANOMOD_REPEAT_BINS -
+ *               1): sizes 1, 2-3, 4-7, ..., 64-127, >= 128
+ *   after_error members that started after a failure of their group had ended:
+ *               with e_end(m) = start_us[m] + max(dur_us[m], 1) — a failed
+ *               call occupies at least one microsecond, so a span never
+ *               follows itself; a sum past 2^64 - 1 lies after every start —
+ *               member i counts iff start_us[i] != 0 and start_us[i] >= the
+ *               least e_end(m) over the members m of its group with err(m)
+ *               and start_us[m] != 0; a group without such an m counts
+ *               nothing, and so does a parallel fan-out with equal starts.
+ *               All zero for a set without a start-time column (timed = 0).
+ * groups + repeats of a row is the number of its spans that have a parent (on
+ * the first S * S rows the edge table's count, for a set without a
+ * self-reference; 0 on the ROOT and ORPHAN rows); retried = recovered +
+ * exhausted; size_hist sums to groups over b, and size_hist[r][0] = groups[r]
+ * - repeated[r].  grouped_spans is the sum of groups + repeats over the rows,
+ * max_size the largest group of the set, timed 1 iff the set has start times.
+ * span_group_size[i] is n of span i's group (0 for a head), span_after_error[i]
+ * 1 iff span i is counted in after_error, by span position; spans outside
+ * every trace read 0 / 0 and are in no group.  Every result is an integer,
+ * bit-exact for any launch geometry.  NULL outputs are skipped; n == 0 gives
+ * zeros; an ungrouped set is ANOMOD_ESTATE; a service index >= n_services is
+ * ANOMOD_EINVAL; at most 2^32 - 2 spans per call.  The call is rank-local: no
+ * collective runs even with a communicator attached (a caller sums the ranks'
+ * tables itself, taking the maximum for size_max).  The set's histogram-form
+ * hint is neither read nor changed; an unknown order hint is probed as in the
+ * self-time call.                                                           */
+#define ANOMOD_REPEAT_BINS 8u
+typedef struct {
+  uint32_t n_services;       /* in : S; E = (S + 2) * S as in anomod_edge_table    */
+  uint32_t max_size;         /* out                                                */
+  uint32_t timed;            /* out                                                */
+  uint64_t grouped_spans;    /* out                                                */
+  uint64_t* groups;          /* [E] host; each array may be NULL                   */
+  uint64_t* repeats;         /* [E]                                                */
+  uint64_t* repeated;        /* [E]                                                */
+  uint64_t* retried;         /* [E]                                                */
+  uint64_t* recovered;       /* [E]                                                */
+  uint64_t* exhausted;       /* [E]                                                */
+  uint64_t* after_error;     /* [E]                                                */
+  uint64_t* size_hist;       /* [E * ANOMOD_REPEAT_BINS] row-major                 */
+  uint32_t* size_max;        /* [E]                                                */
+  uint32_t* span_group_size; /* [n_spans] host, may be NULL                        */
+  uint8_t* span_after_error; /* [n_spans] host, may be NULL                        */
+} anomod_call_repeats;
+int anomod_call_repeats_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                              anomod_call_repeats* out);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
