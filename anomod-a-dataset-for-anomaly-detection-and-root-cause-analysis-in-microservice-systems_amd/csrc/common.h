@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/anomod.h"
+#include "span_word.h"
 
 namespace anomod {
 
@@ -55,7 +56,8 @@ enum HostSlot { kHostGroupAlloc = ANOMOD_HOST_GROUP_ALLOC, kHostGroupPinned = AN
 // learned from one of its own edge tables — every edge with spans gets a code
 // (its rank among those edges) and the bin range [hist_bin(min), hist_bin(max)]
 // of a cell array — and the u32 span-word column written through it (code,
-// error bit and duration of every span position: span_word_pack below).  Owned
+// error bit and either cell + residual or the duration of every span position:
+// the two formats of span_word.h).  Owned
 // by the set (anomod_spans::dense) and released with it; the device to free on
 // is the one current in free_spans.
 struct DenseSet {
@@ -68,6 +70,8 @@ struct DenseSet {
   uint32_t streams = 0;        // row streams at S since the layout was learned
   int tier = 0;                // 0 = small, 1 = large LDS carve
   int wgs_per_cu = 0;          // dense kernel workgroups per CU (0: not asked yet)
+  bool cell_words = false;     // the column holds cell words (fmt), else duration words
+  CellFmt fmt = {0, 0, 0};
   // host layout: 4 words per code {edge, first_bin, base, width}, then the
   // edge -> code table (u16, 0xFFFF = no code) packed two per word
   std::vector<uint32_t> host;
@@ -325,53 +329,6 @@ size_t release_scratch(anomod_ctx* ctx, unsigned keep = 0u);
 hipError_t dev_malloc(anomod_ctx* ctx, void** p, size_t bytes);
 int ensure_host_stage(anomod_ctx* ctx, size_t bytes);
 
-// ---- integer latency histogram (ANOMOD_HIST_*) --------------------------
-__host__ __device__ inline uint32_t hist_bin(uint32_t v) {
-  if (v < 64u) return v;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t lg = 31u - (uint32_t)__clz((int)v);
-#else
-  const uint32_t lg = 31u - (uint32_t)__builtin_clz(v);
-#endif
-  const uint32_t e = lg - ANOMOD_HIST_SUB_BITS;
-  return (e << ANOMOD_HIST_SUB_BITS) + (v >> e);
-}
-
-__host__ __device__ inline void hist_bounds(uint32_t bin, uint32_t* lo, uint32_t* hi) {
-  if (bin < 64u) {
-    *lo = bin;
-    *hi = bin;
-    return;
-  }
-  const uint32_t e = (bin >> ANOMOD_HIST_SUB_BITS) - 1u;
-  const uint64_t m = (uint64_t)(bin & ((1u << ANOMOD_HIST_SUB_BITS) - 1u)) +
-                     (1u << ANOMOD_HIST_SUB_BITS);
-  *lo = (uint32_t)(m << e);
-  *hi = (uint32_t)(((m + 1) << e) - 1);
-}
-
-// ---- span word of the dense edge stream (edge_agg.hip) -------------------
-// One u32 per span position: code << 22 | error << 21 | duration.  The code
-// field holds every code a layout can own (0 .. 511) and kWordNoCode, which
-// none can: "no span here, skip"; the word of all ones is such a word.  A
-// duration above kWordDurMax does not fit: its field is all ones
-// (kWordDurEscape) and the reader takes dur_us at that position instead, so
-// no result rests on durations being small.
-constexpr uint32_t kWordDurBits = 21, kWordCodeBits = 10;
-constexpr uint32_t kWordErrBit = 1u << kWordDurBits;
-constexpr uint32_t kWordCodeShift = kWordDurBits + 1u;
-constexpr uint32_t kWordDurEscape = (1u << kWordDurBits) - 1u;
-constexpr uint32_t kWordDurMax = kWordDurEscape - 1u;  // the largest duration a word holds
-constexpr uint32_t kWordNoCode = (1u << kWordCodeBits) - 1u;
-constexpr uint32_t kWordSkip = 0xFFFFFFFFu;
-static_assert(kWordCodeBits + 1u + kWordDurBits == 32u, "a span word is 32 bits");
-__host__ __device__ inline uint32_t span_word_pack(uint32_t code, bool error, uint32_t dur) {
-  return code << kWordCodeShift | (error ? kWordErrBit : 0u) |
-         (dur <= kWordDurMax ? dur : kWordDurEscape);
-}
-__host__ __device__ inline uint32_t span_word_code(uint32_t w) { return w >> kWordCodeShift; }
-__host__ __device__ inline bool span_word_error(uint32_t w) { return (w & kWordErrBit) != 0u; }
-// the duration field; kWordDurEscape: read dur_us at the span's position
-__host__ __device__ inline uint32_t span_word_dur(uint32_t w) { return w & kWordDurEscape; }
+// (hist_bin / hist_bounds and the span-word formats: span_word.h)
 
 }  // namespace anomod

@@ -54,6 +54,7 @@
 #include "radix.h"
 
 namespace anomod {
+uint64_t env_cap(const char* name, uint64_t floor);  // edge_stream.hip
 namespace {
 
 using namespace chunk;
@@ -1276,7 +1277,7 @@ __global__ __launch_bounds__(kThreads) void edge_row_kernel(
 // those edges) and the bin range [hist_bin(min), hist_bin(max)] of a cell
 // array (DenseSet, common.h).  Once the set's u32 span-word column is written
 // (edge_encode_kernel: code, error bit and duration by span position,
-// span_word_pack in common.h; kWordSkip = no span) an aggregation reads that
+// span_word_pack in span_word.h; kWordSkip = no span) an aggregation reads that
 // column alone, 4 B/span, and a span costs one 16-B LDS read of its code's
 // entry {min, max, base - first_bin, first_bin | width << 16} — few
 // distinct addresses, mostly a broadcast —, one ds_add_u32 on its cell, one
@@ -1328,6 +1329,7 @@ __device__ __forceinline__ uint32_t dense_bin(uint32_t v) {
   return (e << ANOMOD_HIST_SUB_BITS) + (v >> e);
 }
 constexpr int kDenseSmallWgs = 2;  // workgroups per CU of the small carve
+constexpr uint64_t kDenseMaxWgs = 1u << 16;  // (bounds the span cap arithmetic of a launch)
 static_assert(kDenseSmallWgs * DenseLds<0>::kBytes <= 160 * 1024, "LDS budget");
 // Plain row streams of a set between the call that learned its layout and the
 // one that writes the word column.  The column is an investment — a pass of
@@ -1339,11 +1341,26 @@ constexpr uint32_t kDenseAfterStreams = 3;
 
 // lay: 4 words per code {edge, first_bin, base, width} (DenseSet::host).
 // (the small carve is held to 64 registers: two workgroups per CU)
-template <int TIER>
+//
+// FMT 0, duration words: the per-span work described above.  FMT 1, cell
+// words (span_word.h): bin, range check and cell index were resolved when the
+// column was written, so a span costs one compare on its cell field (skip and
+// escape are the two values no cell has), a ds_add_u32 on that cell, a
+// non-returning ds_add_u32 of its residual on a sum replica, one 8-B read of
+// its code's {min key, max key} and one branch around the rare updates (the
+// error bit sits above the key: an error span compares above every max key).
+// The sum needs no carry: a code's sum is sum(count[cell] * lo(bin(cell))),
+// formed in u64 by the wave that flushes the code's cells, plus the residual
+// replicas, which the host keeps below 2^32 by the spans it gives a launch
+// (dense_sum_rounds).  An escaping lane reads dur_us and adds to the HBM
+// tables directly; under the encoder's rule it is never inside its code's
+// range (a bin in range has an exponent <= res_bits and a cell below the
+// reserved values), so it never owns an LDS cell.
+template <int TIER, int FMT>
 __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel(
     const uint32_t* __restrict__ dur, const uint32_t* __restrict__ word,
-    const u32x4* __restrict__ lay, uint32_t ncodes, uint32_t ncells, uint64_t lo, uint64_t hi,
-    Table tab) {
+    const u32x4* __restrict__ lay, uint32_t ncodes, uint32_t ncells, CellFmt fmt, uint64_t lo,
+    uint64_t hi, Table tab) {
   using C = DenseCfg<TIER>;
   using O = DenseLds<TIER>;
   constexpr int kDenseLoad = C::kLoad;
@@ -1354,51 +1371,99 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
   const int tid = threadIdx.x;
   auto* lent = reinterpret_cast<u32x4*>(smem + O::kOffEnt);
   auto* lent1 = reinterpret_cast<uint32_t*>(smem + O::kOffEnt);
+  auto* lkey = reinterpret_cast<u32x2*>(smem + O::kOffEnt);  // FMT 1: {min key, max key}
   auto* lcell = reinterpret_cast<uint32_t*>(smem + O::kOffCell);
   auto* lsum = reinterpret_cast<uint32_t*>(smem + O::kOffSum);
   auto* lerr = reinterpret_cast<uint32_t*>(smem + O::kOffErr);
   auto* lhi = reinterpret_cast<uint32_t*>(smem + O::kOffHi);
   for (uint32_t c = tid; c < ncodes; c += kThreads) {
-    const u32x4 l = lay[c];
-    lent[c] = u32x4{0xFFFFFFFFu, 0u, l.z - l.y, l.y | (l.w << 16)};
+    if constexpr (FMT == 0) {
+      const u32x4 l = lay[c];
+      lent[c] = u32x4{0xFFFFFFFFu, 0u, l.z - l.y, l.y | (l.w << 16)};
+      lhi[c] = 0u;
+    } else {
+      lkey[c] = u32x2{0xFFFFFFFFu, 0u};
+    }
     lerr[c] = 0u;
-    lhi[c] = 0u;
   }
   for (uint32_t k = tid; k < ncells; k += kThreads) lcell[k] = 0u;
   for (uint32_t k = tid; k < ncodes * C::kReps; k += kThreads) lsum[k] = 0u;
   __syncthreads();
   const uint32_t rep = __lane_id() & (C::kReps - 1u);
-  // w: the span word of position g.  A code past the layout's (kWordNoCode: no
-  // span here) is skipped, so no index below leaves the carve; the escape load
-  // is taken by the lanes that need it only.
-  auto one = [&](uint32_t w, uint64_t g) {
-    const uint32_t c = span_word_code(w);
+  const uint32_t key_bits = cell_key_bits(fmt), cell_esc = cell_escape(fmt);
+  // An escaping span of a cell-word column: its duration from dur_us, its
+  // counts to the HBM tables (exact, and rare: nothing here is tuned).
+  auto escaped = [&](uint32_t w, uint64_t g) {
+    const uint32_t c = cell_word_code(fmt, w);
     if (c >= ncodes) return;
-    if constexpr ((ANOMOD_ABL & 96) == 96) {  // keep the loads, do nothing
-      if (w == 0x9E3779B9u) tab.err[0] = w;
-      return;
-    }
-    uint32_t d = span_word_dur(w);
-    if (__builtin_expect(d == kWordDurEscape, 0)) d = dur[g];
-    const u32x4 e = lent[c];
-    const uint32_t bin = dense_bin(d);
-    if constexpr (!(ANOMOD_ABL & 64)) {
-      if (bin - (e.w & 0xFFFFu) < (e.w >> 16))
-        atomicAdd(&lcell[e.z + bin], 1u);
-      else
-        atomicAdd(&tab.hist[(uint64_t)lay[c].x * kBins + bin], 1ull);
-    }
+    const uint32_t d = dur[g], edge = lay[c].x;
+    if constexpr (!(ANOMOD_ABL & 64)) atomicAdd(&tab.hist[(uint64_t)edge * kBins + hist_bin(d)], 1ull);
     if constexpr (!(ANOMOD_ABL & 32)) {
-      // the sum in u32 replicas: an add that wraps its replica (seen in the
-      // value it returns) counts a carry of 2^32 for the code
-      const uint32_t before = atomicAdd(&lsum[c * C::kReps + rep], d);
-      const bool carry = before + d < d, err = span_word_error(w);
-      // one branch around the four rare updates
-      if (__builtin_expect(carry | err | (d < e.x) | (d > e.y), 0)) {
-        if (carry) atomicAdd(&lhi[c], 1u);
-        if (d < e.x) atomicMin(&lent1[4u * c], d);
-        if (d > e.y) atomicMax(&lent1[4u * c + 1u], d);
-        if (err) atomicAdd(&lerr[c], 1u);
+      atomicAdd(&tab.sum[edge], (unsigned long long)d);
+      atomicMin(&tab.mn[edge], d);
+      atomicMax(&tab.mx[edge], d);
+      if ((w >> key_bits) & 1u) atomicAdd(&tab.err[edge], 1ull);
+    }
+  };
+  // w: the span word of position g.  FMT 0: a code past the layout's
+  // (kWordNoCode: no span here) is skipped, so no index below leaves the carve;
+  // the escape load is taken by the lanes that need it only.  FMT 1: a cell
+  // past the layout's is the skip or the escape value; a word with a cell of
+  // the layout was written by edge_encode_kernel with a code of the layout.
+  auto one = [&](uint32_t w, uint64_t g) {
+    if constexpr (FMT == 1) {
+      const uint32_t cell = cell_word_cell(fmt, w);
+      if (__builtin_expect(cell >= ncells, 0)) {
+        if (cell == cell_esc) escaped(w, g);
+        return;
+      }
+      if constexpr ((ANOMOD_ABL & 96) == 96) {  // keep the loads, do nothing
+        if (w == 0x9E3779B9u) tab.err[0] = w;
+        return;
+      }
+      const uint32_t c = cell_word_code(fmt, w);
+      if constexpr (!(ANOMOD_ABL & 64)) atomicAdd(&lcell[cell], 1u);
+      if constexpr (!(ANOMOD_ABL & 32)) {
+        atomicAdd(&lsum[c * C::kReps + rep], cell_word_residual(fmt, w));
+        const u32x2 e = lkey[c];
+        const uint32_t ek = cell_word_ekey(fmt, w);
+        // one branch around the three rare updates: error count, new min key, new max key
+        if (__builtin_expect((ek < e.x) | (ek > e.y), 0)) {
+          const uint32_t key = ek & low_mask(key_bits);
+          if (ek != key) atomicAdd(&lerr[c], 1u);
+          if (key < e.x) atomicMin(&lent1[2u * c], key);
+          if (key > e.y) atomicMax(&lent1[2u * c + 1u], key);
+        }
+      }
+    } else {
+      const uint32_t c = span_word_code(w);
+      if (c >= ncodes) return;
+      if constexpr ((ANOMOD_ABL & 96) == 96) {  // keep the loads, do nothing
+        if (w == 0x9E3779B9u) tab.err[0] = w;
+        return;
+      }
+      uint32_t d = span_word_dur(w);
+      if (__builtin_expect(d == kWordDurEscape, 0)) d = dur[g];
+      const u32x4 e = lent[c];
+      const uint32_t bin = dense_bin(d);
+      if constexpr (!(ANOMOD_ABL & 64)) {
+        if (bin - (e.w & 0xFFFFu) < (e.w >> 16))
+          atomicAdd(&lcell[e.z + bin], 1u);
+        else
+          atomicAdd(&tab.hist[(uint64_t)lay[c].x * kBins + bin], 1ull);
+      }
+      if constexpr (!(ANOMOD_ABL & 32)) {
+        // the sum in u32 replicas: an add that wraps its replica (seen in the
+        // value it returns) counts a carry of 2^32 for the code
+        const uint32_t before = atomicAdd(&lsum[c * C::kReps + rep], d);
+        const bool carry = before + d < d, err = span_word_error(w);
+        // one branch around the four rare updates
+        if (__builtin_expect(carry | err | (d < e.x) | (d > e.y), 0)) {
+          if (carry) atomicAdd(&lhi[c], 1u);
+          if (d < e.x) atomicMin(&lent1[4u * c], d);
+          if (d > e.y) atomicMax(&lent1[4u * c + 1u], d);
+          if (err) atomicAdd(&lerr[c], 1u);
+        }
       }
     }
   };
@@ -1442,27 +1507,49 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     g0 = gn;
   }
   __syncthreads();
-  // Flush: a wave per code, its lanes over the code's cells; then the stats
+  // Flush: a wave per code, its lanes over the code's cells (FMT 1: and the
+  // cells' share of the code's sum, count * lo(bin), in u64); then the stats
   // through code -> edge.  Integer atomics: the tables stay bit-exact.
   const uint32_t wave = (uint32_t)tid / kWave, lane = (uint32_t)tid % kWave;
   for (uint32_t c = wave; c < ncodes; c += kWavesPerWG) {
     const u32x4 l = lay[c];
     unsigned long long* h = tab.hist + (uint64_t)l.x * kBins + l.y;
+    unsigned long long part = 0ull;
     for (uint32_t k = lane; k < l.w; k += kWave) {
       const uint32_t cnt = lcell[l.z + k];
-      if (cnt) atomicAdd(&h[k], (unsigned long long)cnt);
+      if (cnt) {
+        atomicAdd(&h[k], (unsigned long long)cnt);
+        if constexpr (FMT == 1) part += (unsigned long long)cnt * hist_lo(l.y + k);
+      }
+    }
+    if constexpr (FMT == 1 && !(ANOMOD_ABL & 32)) {
+      for (int o = kWave / 2; o > 0; o >>= 1) part += __shfl_xor(part, o);
+      if (lane == 0 && part) atomicAdd(&tab.sum[l.x], part);
     }
   }
   for (uint32_t c = tid; c < ncodes; c += kThreads) {
-    const u32x4 e = lent[c];
-    if (e.x != 0xFFFFFFFFu || e.y != 0u) {
-      const uint32_t edge = lay[c].x;
-      unsigned long long sum = (unsigned long long)lhi[c] << 32;
-      for (uint32_t k = 0; k < C::kReps; ++k) sum += lsum[c * C::kReps + k];
-      atomicAdd(&tab.sum[edge], sum);
-      if (lerr[c]) atomicAdd(&tab.err[edge], (unsigned long long)lerr[c]);
-      atomicMin(&tab.mn[edge], e.x);
-      atomicMax(&tab.mx[edge], e.y);
+    if constexpr (FMT == 1) {
+      const u32x2 e = lkey[c];
+      if (e.x != 0xFFFFFFFFu) {  // (a first span always lowers the min key)
+        const u32x4 l = lay[c];
+        unsigned long long sum = 0ull;
+        for (uint32_t k = 0; k < C::kReps; ++k) sum += lsum[c * C::kReps + k];
+        atomicAdd(&tab.sum[l.x], sum);
+        if (lerr[c]) atomicAdd(&tab.err[l.x], (unsigned long long)lerr[c]);
+        atomicMin(&tab.mn[l.x], cell_key_dur(fmt, e.x, l.y, l.z));
+        atomicMax(&tab.mx[l.x], cell_key_dur(fmt, e.y, l.y, l.z));
+      }
+    } else {
+      const u32x4 e = lent[c];
+      if (e.x != 0xFFFFFFFFu || e.y != 0u) {
+        const uint32_t edge = lay[c].x;
+        unsigned long long sum = (unsigned long long)lhi[c] << 32;
+        for (uint32_t k = 0; k < C::kReps; ++k) sum += lsum[c * C::kReps + k];
+        atomicAdd(&tab.sum[edge], sum);
+        if (lerr[c]) atomicAdd(&tab.err[edge], (unsigned long long)lerr[c]);
+        atomicMin(&tab.mn[edge], e.x);
+        atomicMax(&tab.mx[edge], e.y);
+      }
     }
   }
 }
@@ -1470,13 +1557,15 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
 // The span-word column of spans [lo, hi) from the parent rows, svc_flags and
 // dur_us through the edge -> code table (e2c, u16 per edge, 0xFFFF = the
 // layout has no code for this edge: *bad is set and the set stays on the row
-// stream).  Four span positions per thread; positions outside [lo, hi) are
-// left alone.
+// stream).  cell_words: the code's layout entry (lay, a few KB, cached) says
+// which cell the duration's bin is and cell_word_encode packs cell and
+// residual, or the escape value; else duration words.  Four span positions per
+// thread; positions outside [lo, hi) are left alone.
 __global__ __launch_bounds__(256) void edge_encode_kernel(
     const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
     const uint16_t* __restrict__ rows, const uint16_t* __restrict__ e2c,
-    uint32_t* __restrict__ word, uint64_t lo, uint64_t hi, uint32_t S, uint32_t S0,
-    uint32_t* __restrict__ bad) {
+    const u32x4* __restrict__ lay, bool cell_words, CellFmt fmt, uint32_t* __restrict__ word,
+    uint64_t lo, uint64_t hi, uint32_t S, uint32_t S0, uint32_t* __restrict__ bad) {
   const uint64_t q0 = lo & ~3ull;
   const uint64_t nq = (hi - q0 + 3ull) / 4ull;
   auto enc = [&](uint32_t sf, uint32_t d, uint32_t row) -> uint32_t {
@@ -1487,7 +1576,10 @@ __global__ __launch_bounds__(256) void edge_encode_kernel(
       *bad = 1u;
       return kWordSkip;
     }
-    return span_word_pack(c, ((sf >> 16) & ANOMOD_FLAG_ERROR) != 0u, d);
+    const bool err = ((sf >> 16) & ANOMOD_FLAG_ERROR) != 0u;
+    if (!cell_words) return span_word_pack(c, err, d);
+    const u32x4 l = lay[c];
+    return cell_word_encode(fmt, c, err, d, l.y, l.z, l.w);
   };
   for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq;
        q += (uint64_t)gridDim.x * blockDim.x) {
@@ -1827,6 +1919,21 @@ int launch_rows(anomod_ctx* ctx, const anomod_spans* s, RowFn fn, uint32_t S, ui
 }
 
 // ---- dense stream of a resident set (edge_dense_kernel) ---------------------
+// Spans of a workgroup round (every thread: kLoad groups of 4), and the rounds
+// a workgroup of the cell-word kernel may run in one launch without a sum
+// replica reaching 2^32.  A replica is fed by the kThreads / kReps threads
+// that share its lane bits, 4 * kLoad residuals below 2^res_bits each per
+// round, and by at most one head or tail span (workgroup 0, lanes 0 .. 7).
+uint64_t dense_round_spans(int tier) {
+  return (uint64_t)kThreads * 4 * (tier ? DenseCfg<1>::kLoad : DenseCfg<0>::kLoad);
+}
+uint64_t dense_sum_rounds(int tier, uint32_t res_bits) {
+  const uint64_t per_rep = dense_round_spans(tier) / (tier ? DenseCfg<1>::kReps : DenseCfg<0>::kReps);
+  const uint64_t top = low_mask(res_bits);  // the largest residual
+  if (top == 0) return UINT64_MAX / dense_round_spans(tier) / kDenseMaxWgs;
+  return std::min<uint64_t>((0xFFFFFFFFull / top - 1ull) / per_rep,
+                            UINT64_MAX / dense_round_spans(tier) / kDenseMaxWgs);
+}
 // ANOMOD_EDGE_DENSE=0 is the A/B switch; everything that bypasses the parent
 // rows bypasses this too (the callers ask rows_allowed first).
 bool dense_allowed() {
@@ -1850,10 +1957,12 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
   d.codes = d.cells = 0;
   d.streams = 0;
   d.wgs_per_cu = 0;
+  d.cell_words = false;
   d.host.clear();
   const char* sh = getenv("ANOMOD_DENSE_SHRINK");
   const bool shrink = sh && !strcmp(sh, "1");
   uint64_t codes = 0, cells = 0;
+  uint32_t max_exp = 0;  // the largest bin exponent of any range
   if (E <= kDenseMaxEdges) {
     for (uint32_t e = 0; e < E; ++e) {
       if (!count[e]) continue;
@@ -1869,6 +1978,7 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
       }
       ++codes;
       cells += width;
+      if (width) max_exp = std::max(max_exp, hist_exp(b0 + width - 1u));
     }
   }
   const bool fits = E <= kDenseMaxEdges && codes >= 1 && codes <= DenseCfg<1>::kCodes &&
@@ -1883,12 +1993,25 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
     d.host.resize(at + e2c.size() / 2);
     memcpy(d.host.data() + at, e2c.data(), e2c.size() * 2);
     d.state = DenseSet::kLearned;
+    // Cell words when code, error bit, cell (and its two reserved values) and
+    // the widest residual fit 32 bits, and the residuals of one workgroup round
+    // fit a sum replica; else duration words and the per-span code as before.
+    d.fmt = cell_fmt(d.codes, d.cells, max_exp);
+    d.cell_words = cell_fmt_fits(d.fmt) && dense_sum_rounds(d.tier, d.fmt.res_bits) >= 1;
   } else {
     d.host.clear();
   }
   if (log_kernel())  // (tests)
     fprintf(stderr, "anomod: edge dense layout S=%u codes=%u cells=%u: %s\n", S, d.codes, d.cells,
             !fits ? "does not fit, the set keeps the row stream" : d.tier ? "large" : "small");
+  if (log_kernel() && fits) {
+    if (d.cell_words)
+      fprintf(stderr, "anomod: edge dense words S=%u format=cell code_bits=%u cell_bits=%u res_bits=%u\n",
+              S, d.fmt.code_bits, d.fmt.cell_bits, d.fmt.res_bits);
+    else
+      fprintf(stderr, "anomod: edge dense words S=%u format=dur code_bits=%u cell_bits=0 res_bits=%u\n",
+              S, kWordCodeBits, kWordDurBits);
+  }
 }
 
 // The transition call of a learned layout.  dense_alloc: device room for the layout and
@@ -1933,35 +2056,48 @@ int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h
     const uint64_t blocks = std::min<uint64_t>((nq + 255) / 256, 64ull * ctx->num_cus);
     hipLaunchKernelGGL(edge_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
                        s->svc_flags, s->dur_us, s->parent_row,
-                       reinterpret_cast<const uint16_t*>(base + 4u * d.codes), d.word, s->rows_lo,
-                       s->rows_hi, S, s->rows_S, d_bad);
+                       reinterpret_cast<const uint16_t*>(base + 4u * d.codes),
+                       reinterpret_cast<const u32x4*>(base), d.cell_words, d.fmt, d.word,
+                       s->rows_lo, s->rows_hi, S, s->rows_S, d_bad);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
   ANOMOD_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
   return ANOMOD_OK;
 }
 
-// The set's spans [rows_lo, rows_hi) through the dense kernel of its tier, at
-// most max_launch_spans() per launch (u32 cells).
+// The set's spans [rows_lo, rows_hi) through the dense kernel of its tier and
+// word format, at most max_launch_spans() per launch (u32 cells) and, with
+// cell words, at most dense_sum_rounds() rounds per workgroup (u32 sum
+// replicas without a carry).  ANOMOD_DENSE_WGS caps the grid (tests, A/B).
 int launch_dense(anomod_ctx* ctx, const anomod_spans* s, const Table& tab) {
   DenseSet& d = *s->dense;
-  auto fn = d.tier ? edge_dense_kernel<1> : edge_dense_kernel<0>;
+  auto fn = d.tier ? (d.cell_words ? edge_dense_kernel<1, 1> : edge_dense_kernel<1, 0>)
+                   : (d.cell_words ? edge_dense_kernel<0, 1> : edge_dense_kernel<0, 0>);
   if (d.wgs_per_cu <= 0) {  // resident workgroups per CU, asked once per layout
     int per_cu = 0;
     ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
                         &per_cu, reinterpret_cast<const void*>(fn), kThreads, 0));
     d.wgs_per_cu = std::max(1, std::min(d.tier == 0 ? kDenseSmallWgs : 1, per_cu));
   }
-  const int per_cu = d.wgs_per_cu;
-  const uint64_t cap = max_launch_spans();
-  // spans per workgroup round
-  const uint64_t kRound = (uint64_t)kThreads * 4 * (d.tier ? DenseCfg<1>::kLoad : DenseCfg<0>::kLoad);
+  const uint64_t wgs = std::min<uint64_t>(
+      {(uint64_t)ctx->num_cus * d.wgs_per_cu, env_cap("ANOMOD_DENSE_WGS", 1), kDenseMaxWgs});
+  const uint64_t kRound = dense_round_spans(d.tier);
+  uint64_t cap = max_launch_spans();
+  if (d.cell_words) {
+    const uint64_t by_sum = dense_sum_rounds(d.tier, d.fmt.res_bits) * wgs * kRound;
+    if (by_sum < cap) {
+      cap = by_sum;
+      if (log_kernel() && s->rows_hi - s->rows_lo > cap)  // (tests)
+        fprintf(stderr, "anomod: edge dense sum bound: %llu spans per launch on %llu workgroups\n",
+                (unsigned long long)cap, (unsigned long long)wgs);
+    }
+  }
   for (uint64_t a = s->rows_lo; a < s->rows_hi; a += cap) {
     const uint64_t b = std::min<uint64_t>(s->rows_hi, a + cap);
     const uint64_t want = (b - a + kRound - 1) / kRound;
-    const uint64_t grid = std::min<uint64_t>((uint64_t)ctx->num_cus * per_cu, want);
+    const uint64_t grid = std::min<uint64_t>(wgs, want);
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->dur_us, d.word,
-                       static_cast<const u32x4*>(d.dev), d.codes, d.cells, a, b, tab);
+                       static_cast<const u32x4*>(d.dev), d.codes, d.cells, d.fmt, a, b, tab);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
   return ANOMOD_OK;
