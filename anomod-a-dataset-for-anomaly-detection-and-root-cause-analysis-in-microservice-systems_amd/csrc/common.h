@@ -55,11 +55,11 @@ enum HostSlot { kHostGroupAlloc = ANOMOD_HOST_GROUP_ALLOC, kHostGroupPinned = AN
 // Dense edge stream of a resident set (edge_agg.hip): the layout the set
 // learned from one of its own edge tables — every edge with spans gets a code
 // (its rank among those edges) and the bin range [hist_bin(min), hist_bin(max)]
-// of a cell array — and the u32 span-word column written through it (code,
-// error bit and either cell + residual or the duration of every span position:
-// the two formats of span_word.h).  Owned
-// by the set (anomod_spans::dense) and released with it; the device to free on
-// is the one current in free_spans.
+// of a cell array — and the span-word column written through it, in one of the
+// three formats of span_word.h: u32 words of code, error bit and either cell +
+// residual or the duration of every span position, or the cell word packed into
+// 3 bytes, in two planes.  Owned by the set (anomod_spans::dense) and released
+// with it; the device to free on is the one current in free_spans.
 struct DenseSet {
   enum State { kNone = 0,      // this S was looked at and does not fit (or was rejected)
                kLearned = 1,   // host layout ready, word column not written yet
@@ -71,13 +71,16 @@ struct DenseSet {
   int tier = 0;                // 0 = small, 1 = large LDS carve
   int wgs_per_cu = 0;          // dense kernel workgroups per CU (0: not asked yet)
   bool cell_words = false;     // the column holds cell words (fmt), else duration words
+  bool pack = false;           // ... as packed words (pack_fmt(fmt)): 3 B per span position
   CellFmt fmt = {0, 0, 0};
   // host layout: 4 words per code {edge, first_bin, base, width}, then the
   // edge -> code table (u16, 0xFFFF = no code) packed two per word
   std::vector<uint32_t> host;
-  void* dev = nullptr;         // the same on the device + one flag word
+  void* dev = nullptr;         // the same on the device + the encoder's flag and wide count
   size_t dev_bytes = 0;
   uint32_t* word = nullptr;    // [n_spans]: span words of this S; kWordSkip = no span here
+                               // (pack: u16 [n_spans], then u8 [n_spans] at pack_lo_offset)
+  size_t word_bytes = 0;
   DenseSet() = default;
   DenseSet(const DenseSet&) = delete;
   DenseSet& operator=(const DenseSet&) = delete;
@@ -188,7 +191,7 @@ struct anomod_spans {
   mutable uint32_t rows_S = 0;
   mutable uint64_t rows_lo = 0, rows_hi = 0;
   bool keep_rows = true;
-  // Dense edge stream (edge_agg.hip): layout and u32 span-word column, both
+  // Dense edge stream (edge_agg.hip): layout and span-word column, both
   // functions of the id columns, trace_ptr, svc_flags and the S of the call —
   // none of which a resident set changes (the words also hold dur_us, which it
   // does not change either) — learned from the set's own table.

@@ -1319,6 +1319,9 @@ struct DenseLds {
   static_assert(kBytes <= 160 * 1024, "LDS budget");
   static_assert((C::kReps & (C::kReps - 1u)) == 0u && C::kReps <= (uint32_t)kWave, "replica by lane");
 };
+// A cell of the packed-word kernel (FMT 2), one u32: the owning code in the top
+// byte (the word no longer carries it), a flag, and the count below.
+constexpr uint32_t kPackCodeShift = 24, kPackFlag = 1u << 23, kPackCount = kPackFlag - 1u;
 // hist_bin without its select: below 64 the exponent clamps to 0 and the bin
 // is the value itself (the same bins; clz(0) = 32).
 static_assert(ANOMOD_HIST_SUB_BITS == 5, "values below 2 << SUB_BITS are their own bins");
@@ -1333,11 +1336,32 @@ constexpr uint64_t kDenseMaxWgs = 1u << 16;  // (bounds the span cap arithmetic 
 static_assert(kDenseSmallWgs * DenseLds<0>::kBytes <= 160 * 1024, "LDS budget");
 // Plain row streams of a set between the call that learned its layout and the
 // one that writes the word column.  The column is an investment — a pass of
-// its own (10 B/span read, 4 written: about one row stream) and 4 B/span of
-// memory — that only a set which keeps being aggregated repays, so it is made
+// its own (10 B/span read, 3 or 4 written: about one row stream) and 3 or 4
+// B/span of memory — that only a set which keeps being aggregated repays, so it is made
 // at the set's fifth aggregation: the first four calls of every set run
 // exactly the kernels they ran without the dense stream.
 constexpr uint32_t kDenseAfterStreams = 3;
+
+// The words a thread holds of one round: G load groups (PACK: of 8 span
+// positions, the high halves in w and the low bytes in b).
+template <int G, bool PACK>
+struct DenseRegs {
+  u32x4 w[G];
+};
+template <int G>
+struct DenseRegs<G, true> {
+  u32x4 w[G];
+  u32x2 b[G];
+};
+
+// pack_join of half J & 1 of h and byte J & 3 of b in one byte permute: the
+// selector's bytes pick b's byte, h's two bytes, and zero (v_perm_b32: 0 .. 3
+// are the second operand's bytes, 4 .. 7 the first's, 12 is 0x00).
+template <int J>
+__device__ __forceinline__ uint32_t pack_pick(uint32_t h, uint32_t b) {
+  constexpr uint32_t kSel = 0x0C000000u | (5u + 2u * (J & 1)) << 16 | (4u + 2u * (J & 1)) << 8 | (J & 3);
+  return __builtin_amdgcn_perm(h, b, kSel);
+}
 
 // lay: 4 words per code {edge, first_bin, base, width} (DenseSet::host).
 // (the small carve is held to 64 registers: two workgroups per CU)
@@ -1356,22 +1380,35 @@ constexpr uint32_t kDenseAfterStreams = 3;
 // tables directly; under the encoder's rule it is never inside its code's
 // range (a bin in range has an exponent <= res_bits and a cell below the
 // reserved values), so it never owns an LDS cell.
+//
+// FMT 2, packed words (span_word.h): the cell word in 24 bits, read as groups
+// of 8 span positions from two planes — one 16-B load of the high halves (word
+// as u16) and one 8-B load of the low bytes (wlo) — and taken apart through
+// pack_fmt of the layout (fmt here).  The word has no code: a cell's u32 holds
+// the owning code above its count, filled from lay.  An escape word carries
+// its code in the residual field and goes to `direct`, which reads dur_us: a
+// span outside its code's range counts in HBM as before; a wide span (in
+// range, bin exponent above the residual width) counts in its LDS cell, so the
+// histogram and count * lo(bin) stay in the flush, and gives d - lo(bin), d
+// and the error to the HBM tables.  The at most 7 + 7 span positions of a
+// launch outside its groups of 8 take `direct` too, so a replica never sees
+// them.
 template <int TIER, int FMT>
 __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel(
     const uint32_t* __restrict__ dur, const uint32_t* __restrict__ word,
     const u32x4* __restrict__ lay, uint32_t ncodes, uint32_t ncells, CellFmt fmt, uint64_t lo,
-    uint64_t hi, Table tab) {
+    uint64_t hi, Table tab, const unsigned char* __restrict__ wlo) {
   using C = DenseCfg<TIER>;
   using O = DenseLds<TIER>;
   constexpr int kDenseLoad = C::kLoad;
-  struct Regs {
-    u32x4 w[kDenseLoad];
-  };
+  constexpr int kGroup = FMT == 2 ? 8 : 4;                 // span positions of a load group
+  constexpr int kGroups = kDenseLoad * 4 / kGroup;         // load groups per thread and round
+  using Regs = DenseRegs<kGroups, FMT == 2>;
   __shared__ __attribute__((aligned(16))) unsigned char smem[O::kBytes];
   const int tid = threadIdx.x;
   auto* lent = reinterpret_cast<u32x4*>(smem + O::kOffEnt);
   auto* lent1 = reinterpret_cast<uint32_t*>(smem + O::kOffEnt);
-  auto* lkey = reinterpret_cast<u32x2*>(smem + O::kOffEnt);  // FMT 1: {min key, max key}
+  auto* lkey = reinterpret_cast<u32x2*>(smem + O::kOffEnt);  // FMT 1, 2: {min key, max key}
   auto* lcell = reinterpret_cast<uint32_t*>(smem + O::kOffCell);
   auto* lsum = reinterpret_cast<uint32_t*>(smem + O::kOffSum);
   auto* lerr = reinterpret_cast<uint32_t*>(smem + O::kOffErr);
@@ -1386,14 +1423,47 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     }
     lerr[c] = 0u;
   }
-  for (uint32_t k = tid; k < ncells; k += kThreads) lcell[k] = 0u;
+  if constexpr (FMT == 2) {  // code and flag of every cell: a wave per code, its lanes over the code's cells
+    for (uint32_t c = (uint32_t)tid / kWave; c < ncodes; c += kWavesPerWG) {
+      const u32x4 l = lay[c];
+      for (uint32_t k = (uint32_t)tid % kWave; k < l.w; k += kWave)
+        lcell[l.z + k] = c << kPackCodeShift | kPackFlag;
+    }
+  } else {
+    for (uint32_t k = tid; k < ncells; k += kThreads) lcell[k] = 0u;
+  }
   for (uint32_t k = tid; k < ncodes * C::kReps; k += kThreads) lsum[k] = 0u;
   __syncthreads();
   const uint32_t rep = __lane_id() & (C::kReps - 1u);
   const uint32_t key_bits = cell_key_bits(fmt), cell_esc = cell_escape(fmt);
   // An escaping span of a cell-word column: its duration from dur_us, its
   // counts to the HBM tables (exact, and rare: nothing here is tuned).
+  // FMT 2: span g of code c without its word's help (an escape, or a position
+  // outside the launch's groups of 8).  In range: its LDS cell, and d - lo(bin)
+  // of the sum; the rest to the HBM tables.
+  auto direct = [&](uint32_t c, bool err, uint64_t g) {
+    const u32x4 l = lay[c];
+    const uint32_t d = dur[g], bin = hist_bin(d), k = bin - l.y;
+    uint32_t part = d;
+    if (k < l.w) {
+      if constexpr (!(ANOMOD_ABL & 64)) atomicAdd(&lcell[l.z + k], 1u);
+      part = d - hist_lo(bin);
+    } else {
+      if constexpr (!(ANOMOD_ABL & 64)) atomicAdd(&tab.hist[(uint64_t)l.x * kBins + bin], 1ull);
+    }
+    if constexpr (!(ANOMOD_ABL & 32)) {
+      atomicAdd(&tab.sum[l.x], (unsigned long long)part);
+      atomicMin(&tab.mn[l.x], d);
+      atomicMax(&tab.mx[l.x], d);
+      if (err) atomicAdd(&tab.err[l.x], 1ull);
+    }
+  };
   auto escaped = [&](uint32_t w, uint64_t g) {
+    if constexpr (FMT == 2) {
+      const uint32_t c = pack_word_escape_code(fmt, w);
+      if (c < ncodes) direct(c, pack_word_error(fmt, w), g);
+      return;
+    }
     const uint32_t c = cell_word_code(fmt, w);
     if (c >= ncodes) return;
     const uint32_t d = dur[g], edge = lay[c].x;
@@ -1411,14 +1481,40 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
   // past the layout's is the skip or the escape value; a word with a cell of
   // the layout was written by edge_encode_kernel with a code of the layout.
   auto one = [&](uint32_t w, uint64_t g) {
-    if constexpr (FMT == 1) {
+    if constexpr (FMT >= 1) {
       const uint32_t cell = cell_word_cell(fmt, w);
       if (__builtin_expect(cell >= ncells, 0)) {
         if (cell == cell_esc) escaped(w, g);
         return;
       }
       if constexpr ((ANOMOD_ABL & 96) == 96) {  // keep the loads, do nothing
-        if (w == 0x9E3779B9u) tab.err[0] = w;
+        if (w == (FMT == 2 ? 0x9E3779u : 0x9E3779B9u)) tab.err[0] = w;
+        return;
+      }
+      if constexpr (FMT == 2) {
+        // One returning add on the cell counts the span and brings the cell's
+        // code and flag.  The flag says that a span in this cell may still be
+        // an extreme of its code; the first span that finds its cell strictly
+        // between the code's min and max cells (which only move apart) clears
+        // it, so the {min key, max key} read is left to the tails of a code's
+        // range.  Error spans take the branch for their count.
+        const uint32_t old = atomicAdd(&lcell[cell], 1u), c = old >> kPackCodeShift;
+        if constexpr (!(ANOMOD_ABL & 32)) {
+          atomicAdd(&lsum[c * C::kReps + rep], cell_word_residual(fmt, w));
+          // (nothing above the error bit in a packed word)
+          if (__builtin_expect(((old & kPackFlag) | (w >> key_bits)) != 0u, 0)) {
+            const uint32_t key = w & low_mask(key_bits);
+            if (w != key) atomicAdd(&lerr[c], 1u);
+            if (old & kPackFlag) {
+              u32x2 e = lkey[c];
+              if (key < e.x) atomicMin(&lent1[2u * c], key);
+              if (key > e.y) atomicMax(&lent1[2u * c + 1u], key);
+              e = lkey[c];
+              if (cell > (e.x >> fmt.res_bits) && cell < (e.y >> fmt.res_bits))
+                atomicAnd(&lcell[cell], ~kPackFlag);
+            }
+          }
+        }
         return;
       }
       const uint32_t c = cell_word_code(fmt, w);
@@ -1467,27 +1563,45 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
       }
     }
   };
-  const uint64_t up = (lo + 3ull) & ~3ull;
+  constexpr uint64_t kG = kGroup, kGm = kG - 1ull;
+  const uint64_t up = (lo + kGm) & ~kGm;
   const uint64_t a0 = up < hi ? up : hi;                      // head [lo, a0)
-  const uint64_t a1 = (hi & ~3ull) > a0 ? (hi & ~3ull) : a0;  // groups [a0, a1), tail [a1, hi)
-  if (blockIdx.x == 0 && tid < 8) {
-    const uint64_t g = tid < 4 ? lo + (uint64_t)tid : a1 + (uint64_t)(tid - 4);
-    if (g < (tid < 4 ? a0 : hi)) one(word[g], g);
+  const uint64_t a1 = (hi & ~kGm) > a0 ? (hi & ~kGm) : a0;    // groups [a0, a1), tail [a1, hi)
+  if (blockIdx.x == 0 && tid < 2 * kGroup) {
+    const uint64_t g = tid < kGroup ? lo + (uint64_t)tid : a1 + (uint64_t)(tid - kGroup);
+    if (g < (tid < kGroup ? a0 : hi)) {
+      if constexpr (FMT == 2) {
+        const uint32_t w = pack_join(reinterpret_cast<const uint16_t*>(word)[g], wlo[g]);
+        const uint32_t cell = cell_word_cell(fmt, w);
+        if (cell < ncells)
+          direct(lcell[cell] >> kPackCodeShift, pack_word_error(fmt, w), g);
+        else if (cell == cell_esc)
+          escaped(w, g);
+      } else {
+        one(word[g], g);
+      }
+    }
   }
-  const uint64_t ng = (a1 - a0) / 4;
-  const u32x4* w4 = reinterpret_cast<const u32x4*>(word + a0);
+  const uint64_t ng = (a1 - a0) / kG;
+  // (FMT 2: a0 is a multiple of 8, so both planes' groups are aligned)
+  const u32x4* w4 = FMT == 2 ? reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(word) + a0)
+                             : reinterpret_cast<const u32x4*>(word + a0);
   // groups past the end re-read the last one (no branch around a load) and
   // take skip words
   auto load = [&](uint64_t g0, Regs& R) {
 #pragma unroll
-    for (int j = 0; j < kDenseLoad; ++j) {
+    for (int j = 0; j < kGroups; ++j) {
       const uint64_t gi = g0 + (uint64_t)(j * kThreads + tid);
       const uint64_t gc = gi < ng ? gi : ng - 1;
       const u32x4 w = w4[gc];
       R.w[j] = gi < ng ? w : u32x4{kWordSkip, kWordSkip, kWordSkip, kWordSkip};
+      if constexpr (FMT == 2) {
+        const u32x2 b = reinterpret_cast<const u32x2*>(wlo + a0)[gc];
+        R.b[j] = gi < ng ? b : u32x2{kWordSkip, kWordSkip};
+      }
     }
   };
-  constexpr uint64_t kPerBlock = (uint64_t)kThreads * kDenseLoad;
+  constexpr uint64_t kPerBlock = (uint64_t)kThreads * kGroups;
   uint64_t g0 = (uint64_t)blockIdx.x * kPerBlock;
   Regs cur;
   if (g0 < ng) load(g0, cur);
@@ -1496,18 +1610,32 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     Regs nxt = cur;
     if (gn < ng) load(gn, nxt);
 #pragma unroll
-    for (int j = 0; j < kDenseLoad; ++j) {
-      const uint64_t g = a0 + 4ull * (g0 + (uint64_t)(j * kThreads + tid));
-      one(cur.w[j].x, g);
-      one(cur.w[j].y, g + 1);
-      one(cur.w[j].z, g + 2);
-      one(cur.w[j].w, g + 3);
+    for (int j = 0; j < kGroups; ++j) {
+      const uint64_t g = a0 + kG * (g0 + (uint64_t)(j * kThreads + tid));
+      if constexpr (FMT == 2) {
+        const u32x4 h = cur.w[j];
+        const u32x2 b = cur.b[j];
+        // span j of the group: half j & 1 of h[j / 2] above byte j & 3 of b[j / 4]
+        one(pack_pick<0>(h.x, b.x), g);
+        one(pack_pick<1>(h.x, b.x), g + 1);
+        one(pack_pick<2>(h.y, b.x), g + 2);
+        one(pack_pick<3>(h.y, b.x), g + 3);
+        one(pack_pick<0>(h.z, b.y), g + 4);
+        one(pack_pick<1>(h.z, b.y), g + 5);
+        one(pack_pick<2>(h.w, b.y), g + 6);
+        one(pack_pick<3>(h.w, b.y), g + 7);
+      } else {
+        one(cur.w[j].x, g);
+        one(cur.w[j].y, g + 1);
+        one(cur.w[j].z, g + 2);
+        one(cur.w[j].w, g + 3);
+      }
     }
     cur = nxt;
     g0 = gn;
   }
   __syncthreads();
-  // Flush: a wave per code, its lanes over the code's cells (FMT 1: and the
+  // Flush: a wave per code, its lanes over the code's cells (FMT 1, 2: and the
   // cells' share of the code's sum, count * lo(bin), in u64); then the stats
   // through code -> edge.  Integer atomics: the tables stay bit-exact.
   const uint32_t wave = (uint32_t)tid / kWave, lane = (uint32_t)tid % kWave;
@@ -1516,19 +1644,19 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     unsigned long long* h = tab.hist + (uint64_t)l.x * kBins + l.y;
     unsigned long long part = 0ull;
     for (uint32_t k = lane; k < l.w; k += kWave) {
-      const uint32_t cnt = lcell[l.z + k];
+      const uint32_t cnt = FMT == 2 ? lcell[l.z + k] & kPackCount : lcell[l.z + k];
       if (cnt) {
         atomicAdd(&h[k], (unsigned long long)cnt);
-        if constexpr (FMT == 1) part += (unsigned long long)cnt * hist_lo(l.y + k);
+        if constexpr (FMT >= 1) part += (unsigned long long)cnt * hist_lo(l.y + k);
       }
     }
-    if constexpr (FMT == 1 && !(ANOMOD_ABL & 32)) {
+    if constexpr (FMT >= 1 && !(ANOMOD_ABL & 32)) {
       for (int o = kWave / 2; o > 0; o >>= 1) part += __shfl_xor(part, o);
       if (lane == 0 && part) atomicAdd(&tab.sum[l.x], part);
     }
   }
   for (uint32_t c = tid; c < ncodes; c += kThreads) {
-    if constexpr (FMT == 1) {
+    if constexpr (FMT >= 1) {
       const u32x2 e = lkey[c];
       if (e.x != 0xFFFFFFFFu) {  // (a first span always lowers the min key)
         const u32x4 l = lay[c];
@@ -1599,6 +1727,69 @@ __global__ __launch_bounds__(256) void edge_encode_kernel(
         word[i] = enc(svcfl[i], dur[i], rows[i]);
     }
   }
+}
+
+// The same for a packing layout (p = pack_fmt of its widths): the two planes of
+// the packed words, eight span positions per thread — one 16-B store of the
+// high halves, one 8-B store of the low bytes — and the wide spans counted
+// into *wide, one atomic per wave.
+__global__ __launch_bounds__(256) void edge_encode_pack_kernel(
+    const uint32_t* __restrict__ svcfl, const uint32_t* __restrict__ dur,
+    const uint16_t* __restrict__ rows, const uint16_t* __restrict__ e2c,
+    const u32x4* __restrict__ lay, CellFmt p, uint16_t* __restrict__ whi,
+    unsigned char* __restrict__ wlo, uint64_t lo, uint64_t hi, uint32_t S, uint32_t S0,
+    uint32_t* __restrict__ bad, unsigned long long* __restrict__ wide) {
+  const uint64_t q0 = lo & ~7ull;
+  const uint64_t nq = (hi - q0 + 7ull) / 8ull;
+  uint32_t nwide = 0u;
+  auto enc = [&](uint32_t sf, uint32_t d, uint32_t row) -> uint32_t {
+    if (row == 0xFFFFu) return kPackSkip;
+    const uint32_t pr = row >= S0 ? row - S0 + S : row;
+    const uint32_t c = e2c[pr * S + (sf & 0xFFFFu)];
+    if (c == 0xFFFFu) {
+      *bad = 1u;
+      return kPackSkip;
+    }
+    const u32x4 l = lay[c];
+    bool w = false;
+    const uint32_t word = pack_word_encode(p, c, ((sf >> 16) & ANOMOD_FLAG_ERROR) != 0u, d, l.y, l.z,
+                                           l.w, &w);
+    nwide += w ? 1u : 0u;
+    return word;
+  };
+  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq;
+       q += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t g = q0 + 8ull * q;
+    if (g >= lo && g + 8ull <= hi) {
+      const u32x4 s0 = *reinterpret_cast<const u32x4*>(svcfl + g);
+      const u32x4 s1 = *reinterpret_cast<const u32x4*>(svcfl + g + 4);
+      const u32x4 d0 = *reinterpret_cast<const u32x4*>(dur + g);
+      const u32x4 d1 = *reinterpret_cast<const u32x4*>(dur + g + 4);
+      const u32x4 rw = *reinterpret_cast<const u32x4*>(rows + g);
+      const uint32_t w[8] = {enc(s0.x, d0.x, rw.x & 0xFFFFu), enc(s0.y, d0.y, rw.x >> 16),
+                             enc(s0.z, d0.z, rw.y & 0xFFFFu), enc(s0.w, d0.w, rw.y >> 16),
+                             enc(s1.x, d1.x, rw.z & 0xFFFFu), enc(s1.y, d1.y, rw.z >> 16),
+                             enc(s1.z, d1.z, rw.w & 0xFFFFu), enc(s1.w, d1.w, rw.w >> 16)};
+      u32x4 h;
+      h.x = (w[0] >> 8) | (w[1] >> 8) << 16;
+      h.y = (w[2] >> 8) | (w[3] >> 8) << 16;
+      h.z = (w[4] >> 8) | (w[5] >> 8) << 16;
+      h.w = (w[6] >> 8) | (w[7] >> 8) << 16;
+      u32x2 b;
+      b.x = (w[0] & 0xFFu) | (w[1] & 0xFFu) << 8 | (w[2] & 0xFFu) << 16 | w[3] << 24;
+      b.y = (w[4] & 0xFFu) | (w[5] & 0xFFu) << 8 | (w[6] & 0xFFu) << 16 | w[7] << 24;
+      *reinterpret_cast<u32x4*>(whi + g) = h;
+      *reinterpret_cast<u32x2*>(wlo + g) = b;
+    } else {
+      for (uint64_t i = g < lo ? lo : g; i < g + 8ull && i < hi; ++i) {
+        const uint32_t w = enc(svcfl[i], dur[i], rows[i]);
+        whi[i] = pack_hi(w);
+        wlo[i] = pack_lo(w);
+      }
+    }
+  }
+  for (int o = kWave / 2; o > 0; o >>= 1) nwide += __shfl_xor(nwide, o);
+  if (threadIdx.x % kWave == 0 && nwide) atomicAdd(wide, (unsigned long long)nwide);
 }
 
 // Count + nearest-rank quantiles per edge from the merged histogram: one
@@ -1940,6 +2131,11 @@ bool dense_allowed() {
   const char* f = getenv("ANOMOD_EDGE_DENSE");
   return !(f && !strcmp(f, "0"));
 }
+// ANOMOD_DENSE_PACK=0: a layout that would pack keeps 4-byte cell words (A/B).
+bool pack_allowed() {
+  const char* f = getenv("ANOMOD_DENSE_PACK");
+  return !(f && !strcmp(f, "0"));
+}
 
 // The set's layout for S from one of its own tables (count / min / max per
 // edge, on the host): codes by edge order, bin ranges back to back in the
@@ -1957,7 +2153,7 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
   d.codes = d.cells = 0;
   d.streams = 0;
   d.wgs_per_cu = 0;
-  d.cell_words = false;
+  d.cell_words = d.pack = false;
   d.host.clear();
   const char* sh = getenv("ANOMOD_DENSE_SHRINK");
   const bool shrink = sh && !strcmp(sh, "1");
@@ -1998,6 +2194,9 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
     // fit a sum replica; else duration words and the per-span code as before.
     d.fmt = cell_fmt(d.codes, d.cells, max_exp);
     d.cell_words = cell_fmt_fits(d.fmt) && dense_sum_rounds(d.tier, d.fmt.res_bits) >= 1;
+    // ... and packed, 3 B per span, when the layout also keeps to 256 codes and
+    // 15 cell bits (span_word.h)
+    d.pack = d.cell_words && pack_allowed() && pack_fmt_fits(d.fmt, d.codes);
   } else {
     d.host.clear();
   }
@@ -2011,6 +2210,9 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
     else
       fprintf(stderr, "anomod: edge dense words S=%u format=dur code_bits=%u cell_bits=0 res_bits=%u\n",
               S, kWordCodeBits, kWordDurBits);
+    if (d.pack)
+      fprintf(stderr, "anomod: edge dense pack S=%u bytes=3 cell_bits=%u res_bits=%u\n", S,
+              pack_fmt(d.fmt).cell_bits, pack_fmt(d.fmt).res_bits);
   }
 }
 
@@ -2019,9 +2221,14 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
 // stream).  dense_encode: the layout to the device and the word column of
 // [rows_lo, rows_hi), queued after the row stream of this call; the flag word
 // comes back into *h_bad with the table.
+size_t dense_flag_offset(const DenseSet& d) { return (d.host.size() * 4 + 7) & ~size_t(7); }
+unsigned char* dense_lo_plane(const DenseSet& d, const anomod_spans* s) {
+  return reinterpret_cast<unsigned char*>(d.word) + pack_lo_offset(s->n_spans);
+}
 bool dense_alloc(anomod_ctx* ctx, const anomod_spans* s) {
   DenseSet& d = *s->dense;
-  const size_t bytes = d.host.size() * 4 + 4;
+  // (the layout, then the encoder's flag word and its u64 count of wide spans)
+  const size_t bytes = dense_flag_offset(d) + 16;
   if (d.dev_bytes < bytes) {
     if (d.dev) (void)hipFree(d.dev);
     d.dev = nullptr;
@@ -2033,13 +2240,18 @@ bool dense_alloc(anomod_ctx* ctx, const anomod_spans* s) {
     }
     d.dev_bytes = bytes;
   }
-  if (!d.word) {
+  const size_t need = d.pack ? pack_column_bytes(s->n_spans) : s->n_spans * 4;
+  if (d.word_bytes < need) {
+    if (d.word) (void)hipFree(d.word);
+    d.word = nullptr;
+    d.word_bytes = 0;
     void* p = nullptr;
-    if (dev_malloc(ctx, &p, s->n_spans * 4) != hipSuccess) {
+    if (dev_malloc(ctx, &p, need) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
     d.word = static_cast<uint32_t*>(p);
+    d.word_bytes = need;
   }
   return true;
 }
@@ -2047,12 +2259,23 @@ bool dense_alloc(anomod_ctx* ctx, const anomod_spans* s) {
 int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h_bad) {
   DenseSet& d = *s->dense;
   auto* base = static_cast<uint32_t*>(d.dev);
-  uint32_t* d_bad = base + d.host.size();
+  auto* d_bad = reinterpret_cast<uint32_t*>(static_cast<char*>(d.dev) + dense_flag_offset(d));
   ANOMOD_HIP(ctx, hipMemcpyAsync(base, d.host.data(), d.host.size() * 4, hipMemcpyHostToDevice,
                                  ctx->stream));
-  ANOMOD_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
+  ANOMOD_HIP(ctx, hipMemsetAsync(d_bad, 0, 16, ctx->stream));
   const uint64_t nq = (s->rows_hi - (s->rows_lo & ~3ull) + 3) / 4;
-  if (nq) {
+  if (nq && d.pack) {
+    const uint64_t n8 = (s->rows_hi - (s->rows_lo & ~7ull) + 7) / 8;
+    const uint64_t blocks = std::min<uint64_t>((n8 + 255) / 256, 64ull * ctx->num_cus);
+    hipLaunchKernelGGL(edge_encode_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
+                       s->svc_flags, s->dur_us, s->parent_row,
+                       reinterpret_cast<const uint16_t*>(base + 4u * d.codes),
+                       reinterpret_cast<const u32x4*>(base), pack_fmt(d.fmt),
+                       reinterpret_cast<uint16_t*>(d.word), dense_lo_plane(d, s), s->rows_lo,
+                       s->rows_hi, S, s->rows_S, d_bad,
+                       reinterpret_cast<unsigned long long*>(d_bad + 2));
+    ANOMOD_HIP(ctx, hipGetLastError());
+  } else if (nq) {
     const uint64_t blocks = std::min<uint64_t>((nq + 255) / 256, 64ull * ctx->num_cus);
     hipLaunchKernelGGL(edge_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
                        s->svc_flags, s->dur_us, s->parent_row,
@@ -2061,7 +2284,7 @@ int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h
                        s->rows_lo, s->rows_hi, S, s->rows_S, d_bad);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
-  ANOMOD_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+  ANOMOD_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 16, hipMemcpyDeviceToHost, ctx->stream));
   return ANOMOD_OK;
 }
 
@@ -2071,8 +2294,9 @@ int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h
 // replicas without a carry).  ANOMOD_DENSE_WGS caps the grid (tests, A/B).
 int launch_dense(anomod_ctx* ctx, const anomod_spans* s, const Table& tab) {
   DenseSet& d = *s->dense;
-  auto fn = d.tier ? (d.cell_words ? edge_dense_kernel<1, 1> : edge_dense_kernel<1, 0>)
-                   : (d.cell_words ? edge_dense_kernel<0, 1> : edge_dense_kernel<0, 0>);
+  const int f = d.pack ? 2 : d.cell_words ? 1 : 0;
+  auto fn = d.tier ? (f == 2 ? edge_dense_kernel<1, 2> : f ? edge_dense_kernel<1, 1> : edge_dense_kernel<1, 0>)
+                   : (f == 2 ? edge_dense_kernel<0, 2> : f ? edge_dense_kernel<0, 1> : edge_dense_kernel<0, 0>);
   if (d.wgs_per_cu <= 0) {  // resident workgroups per CU, asked once per layout
     int per_cu = 0;
     ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
@@ -2092,12 +2316,16 @@ int launch_dense(anomod_ctx* ctx, const anomod_spans* s, const Table& tab) {
                 (unsigned long long)cap, (unsigned long long)wgs);
     }
   }
+  // (packed words: a cell counts in 23 bits a workgroup's rounds and its head and tail spans)
+  if (d.pack) cap = std::min<uint64_t>(cap, (kPackCount - 14u) / kRound * kRound * wgs);
   for (uint64_t a = s->rows_lo; a < s->rows_hi; a += cap) {
     const uint64_t b = std::min<uint64_t>(s->rows_hi, a + cap);
     const uint64_t want = (b - a + kRound - 1) / kRound;
     const uint64_t grid = std::min<uint64_t>(wgs, want);
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(kThreads), 0, ctx->stream, s->dur_us, d.word,
-                       static_cast<const u32x4*>(d.dev), d.codes, d.cells, d.fmt, a, b, tab);
+                       static_cast<const u32x4*>(d.dev), d.codes, d.cells,
+                       d.pack ? pack_fmt(d.fmt) : d.fmt, a, b, tab,
+                       d.pack ? dense_lo_plane(d, s) : nullptr);
     ANOMOD_HIP(ctx, hipGetLastError());
   }
   return ANOMOD_OK;
@@ -2499,7 +2727,7 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   // (+ 16: the span range of a filled column)
   const size_t small = (L.end_small - L.off_err + 7) & ~size_t(7);
   if (local == ANOMOD_OK) local = ensure_table(ctx, L.bytes);
-  if (local == ANOMOD_OK) local = ensure_host_stage(ctx, small + 32);  // + the encoder's flag
+  if (local == ANOMOD_OK) local = ensure_host_stage(ctx, small + 32);  // + the encoder's flag and count
   if (int rc = comm_agree(ctx, local)) return rc;
   Table tab = table_at(ctx, L, E);
   if (build) tab.bpar = spans->parent_row;
@@ -2627,6 +2855,24 @@ int anomod_edge_aggregate_spans(anomod_ctx* ctx, const anomod_spans* spans, uint
   if (learn) spans->hist_form = ovf[1] <= kPairSlots / 2 ? 0 : 1;
   if (dense_enc) {  // an edge without a code (never from this set's own table): row stream
     ds->state = *h_bad ? DenseSet::kNone : DenseSet::kCoded;
+    // More than 1/256 of the positions wide (each costs the dense kernel a
+    // 32-B sector of dur_us): the set gives up the packed form and this call
+    // writes the column again, as 4-byte cell words, for the calls after it.
+    const unsigned long long wide = *reinterpret_cast<const unsigned long long*>(h_bad + 2);
+    const unsigned long long n_enc = spans->rows_hi - spans->rows_lo;
+    if (ds->pack && ds->state == DenseSet::kCoded && wide * 256ull > n_enc) {
+      if (log_kernel())  // (tests)
+        fprintf(stderr, "anomod: edge dense pack S=%u dropped: %llu wide of %llu spans\n", S, wide,
+                n_enc);
+      ds->pack = false;
+      ds->wgs_per_cu = 0;  // (another kernel from here on)
+      ds->state = DenseSet::kNone;
+      if (dense_alloc(ctx, spans)) {
+        if (int rc = dense_encode(ctx, spans, S, h_bad)) return rc;
+        if (int rc = stream_wait(ctx)) return rc;
+        ds->state = *h_bad ? DenseSet::kNone : DenseSet::kCoded;
+      }
+    }
   } else if (dense_wait) {
     ++ds->streams;
   } else if ((build || stream) && dense_try && !dense_run && !(ds && ds->S == S)) {

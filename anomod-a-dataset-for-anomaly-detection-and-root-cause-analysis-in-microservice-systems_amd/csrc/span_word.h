@@ -1,4 +1,4 @@
-// The integer latency histogram's bins and the two span-word formats of the
+// The integer latency histogram's bins and the three span-word formats of the
 // dense edge stream (edge_agg.hip).  Plain C++ with no HIP dependency: the
 // library includes it through common.h, and the host test of the formats
 // (fuzz/span_word_check.cpp) builds it alone.
@@ -141,5 +141,53 @@ ANOMOD_HD inline uint32_t cell_word_ekey(CellFmt f, uint32_t w) {
 ANOMOD_HD inline uint32_t cell_key_dur(CellFmt f, uint32_t key, uint32_t first_bin, uint32_t base) {
   return hist_lo(first_bin + (key >> f.res_bits) - base) + (key & low_mask(f.res_bits));
 }
+
+// ---- packed word: the third format, a cell word in 24 bits ------------------
+// The codes of a layout own back-to-back ranges of its cell array, so the
+// absolute cell already names the code, and almost no span needs the widest
+// residual.  For a layout of widths f the packed word holds, from the top,
+//   error | cell | residual              (unused bits above the error bit: 0)
+// with the same cell and the same two reserved cells, in pack_fmt(f): no code
+// field and pr = min(max(res_bits, code_bits), 23 - cell_bits) residual bits,
+// 1 + cell_bits + pr <= 24.  Every cell-word function above reads it through
+// pack_fmt(f) (the code aside).  A span escapes when it is not in its code's
+// range, as before, and also when its bin's exponent exceeds pr (a wide span:
+// in range, but its residual does not fit); an escape word keeps the error
+// bit and carries the code in the residual field, which is therefore never
+// narrower than code_bits, and has room for the 256 codes a packing layout may
+// have because cell_bits <= 15.  Within a code the key still grows strictly
+// with d over the spans that do not escape.
+// The column keeps the word in two planes, the high 16 bits as u16 and the low
+// 8 as u8 by span position (pack_split / pack_join): 3 B per span.
+constexpr uint32_t kPackBits = 24, kPackMaxCodes = 256, kPackMaxCellBits = 15;
+constexpr uint32_t kPackSkip = (1u << kPackBits) - 1u;  // all ones: a skip word under every width
+ANOMOD_HD inline bool pack_fmt_fits(CellFmt f, uint32_t codes) {
+  return cell_fmt_fits(f) && codes <= kPackMaxCodes && f.cell_bits <= kPackMaxCellBits;
+}
+ANOMOD_HD inline CellFmt pack_fmt(CellFmt f) {
+  const uint32_t room = kPackBits - 1u - f.cell_bits;
+  const uint32_t want = f.res_bits > f.code_bits ? f.res_bits : f.code_bits;
+  return CellFmt{0u, f.cell_bits, want < room ? want : room};
+}
+// The packed word of duration d under code's layout entry; p = pack_fmt(f).
+// *wide is set for an escaping span that lies inside the code's range.
+ANOMOD_HD inline uint32_t pack_word_encode(CellFmt p, uint32_t code, bool error, uint32_t d,
+                                           uint32_t first_bin, uint32_t base, uint32_t width,
+                                           bool* wide) {
+  const uint32_t bin = hist_bin(d), k = bin - first_bin, cell = base + k;
+  const bool in_range = k < width && cell < cell_escape(p);
+  *wide = in_range && hist_exp(bin) > p.res_bits;
+  if (in_range && !*wide) return cell_word_pack(p, 0u, error, cell, d - hist_lo(bin));
+  return cell_word_pack(p, 0u, error, cell_escape(p), code);
+}
+// the code an escape word carries
+ANOMOD_HD inline uint32_t pack_word_escape_code(CellFmt p, uint32_t w) { return w & low_mask(p.res_bits); }
+ANOMOD_HD inline bool pack_word_error(CellFmt p, uint32_t w) { return ((w >> cell_key_bits(p)) & 1u) != 0u; }
+ANOMOD_HD inline uint16_t pack_hi(uint32_t w) { return (uint16_t)(w >> 8); }
+ANOMOD_HD inline uint8_t pack_lo(uint32_t w) { return (uint8_t)(w & 0xFFu); }
+ANOMOD_HD inline uint32_t pack_join(uint32_t hi16, uint32_t lo8) { return hi16 << 8 | lo8; }
+// byte offset of the u8 plane in a column of n span positions (16-B aligned)
+ANOMOD_HD inline uint64_t pack_lo_offset(uint64_t n) { return (2ull * n + 15ull) & ~15ull; }
+ANOMOD_HD inline uint64_t pack_column_bytes(uint64_t n) { return pack_lo_offset(n) + n; }
 
 }  // namespace anomod
