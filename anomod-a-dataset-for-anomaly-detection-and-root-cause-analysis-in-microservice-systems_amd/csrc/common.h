@@ -72,6 +72,8 @@ struct DenseSet {
   int wgs_per_cu = 0;          // dense kernel workgroups per CU (0: not asked yet)
   bool cell_words = false;     // the column holds cell words (fmt), else duration words
   bool pack = false;           // ... as packed words (pack_fmt(fmt)): 3 B per span position
+  bool errcells = false;       // packed, small carve: the kernel keeps a cell's error spans in
+                               // an entry of their own (edge_dense_kernel<0, 3>)
   CellFmt fmt = {0, 0, 0};
   // host layout: 4 words per code {edge, first_bin, base, width}, then the
   // edge -> code table (u16, 0xFFFF = no code) packed two per word

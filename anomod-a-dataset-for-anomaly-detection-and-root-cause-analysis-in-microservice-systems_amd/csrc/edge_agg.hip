@@ -1291,7 +1291,9 @@ __global__ __launch_bounds__(kThreads) void edge_row_kernel(
 // ranges: a span whose bin lies outside its code's range (one unsigned
 // compare) counts in tab.hist in HBM.  Two static LDS carves: small (<= 64
 // codes, <= 8 Ki cells, 32 sum replicas: the SocialNetwork sets) and large
-// (<= 512 codes, <= 32 Ki cells, 8 sum replicas, under 160 KiB).
+// (<= 512 codes, <= 32 Ki cells, 8 sum replicas, under 160 KiB).  A packed
+// layout of the small carve whose cells fit twice takes a third, the small
+// carve with 16 Ki entries (error cells, FMT 3 below).
 constexpr uint32_t kDenseMaxEdges = 1u << 16;  // edge -> code table: at most 128 KiB
 template <int TIER>
 struct DenseCfg;
@@ -1304,6 +1306,12 @@ template <>
 struct DenseCfg<1> {
   static constexpr uint32_t kCodes = 512, kCells = 32768, kReps = 8;
   static constexpr int kLoad = 8;
+};
+// The small carve with error cells (FMT 3): kCells counts entries, two per cell.
+template <>
+struct DenseCfg<2> {
+  static constexpr uint32_t kCodes = 64, kCells = 16384, kReps = 32;
+  static constexpr int kLoad = 4;
 };
 static_assert(DenseCfg<1>::kCodes <= kWordNoCode, "the code field holds every code and the skip value");
 static_assert(DenseCfg<0>::kCodes <= DenseCfg<1>::kCodes, "one word format for both tiers");
@@ -1334,6 +1342,10 @@ __device__ __forceinline__ uint32_t dense_bin(uint32_t v) {
 constexpr int kDenseSmallWgs = 2;  // workgroups per CU of the small carve
 constexpr uint64_t kDenseMaxWgs = 1u << 16;  // (bounds the span cap arithmetic of a launch)
 static_assert(kDenseSmallWgs * DenseLds<0>::kBytes <= 160 * 1024, "LDS budget");
+static_assert(kDenseSmallWgs * DenseLds<2>::kBytes <= 160 * 1024, "LDS budget");
+static_assert(DenseCfg<2>::kLoad == DenseCfg<0>::kLoad && DenseCfg<2>::kReps == DenseCfg<0>::kReps &&
+                  DenseCfg<2>::kCodes == DenseCfg<0>::kCodes,
+              "the launch bounds of the small carve hold for both of its forms");
 // Plain row streams of a set between the call that learned its layout and the
 // one that writes the word column.  The column is an investment — a pass of
 // its own (10 B/span read, 3 or 4 written: about one row stream) and 3 or 4
@@ -1393,17 +1405,34 @@ __device__ __forceinline__ uint32_t pack_pick(uint32_t h, uint32_t b) {
 // and the error to the HBM tables.  The at most 7 + 7 span positions of a
 // launch outside its groups of 8 take `direct` too, so a replica never sees
 // them.
+//
+// FMT 3, packed words with error cells (small carve only, DenseCfg<2>): the
+// same column, but the cell array has 16 Ki entries and a cell two of them —
+// its own, and 2^cell_bits above it the one its error spans count in; the
+// entry of a word is w >> res_bits (pack_word_entry).  FMT 2 takes its rare
+// branch for every error span, which at 0.5 % errors is 27 % of a wave's
+// spans (1 - 0.995^64); here the error count of a code is the sum of its
+// error entries, formed by the wave that flushes the code's cells, lerr is
+// not used, and the branch is taken on the entry's flag alone.  A span that
+// finds its cell strictly inside its code's range clears the flag of both
+// entries of the cell.  `direct` counts in the cell's own entry and sends its
+// error to tab.err, as in FMT 2.  A layout takes this form when
+// 2^cell_bits + cells <= 16 Ki (dense_learn; ANOMOD_DENSE_ERRCELLS=0 keeps
+// FMT 2); 75,264 B of LDS, still two workgroups per CU.
 template <int TIER, int FMT>
 __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel(
     const uint32_t* __restrict__ dur, const uint32_t* __restrict__ word,
     const u32x4* __restrict__ lay, uint32_t ncodes, uint32_t ncells, CellFmt fmt, uint64_t lo,
     uint64_t hi, Table tab, const unsigned char* __restrict__ wlo) {
-  using C = DenseCfg<TIER>;
-  using O = DenseLds<TIER>;
+  static_assert(FMT != 3 || TIER == 0, "error cells: the small carve only");
+  constexpr bool kPacked = FMT >= 2, kErrCells = FMT == 3;
+  constexpr int kCarve = kErrCells ? 2 : TIER;
+  using C = DenseCfg<kCarve>;
+  using O = DenseLds<kCarve>;
   constexpr int kDenseLoad = C::kLoad;
-  constexpr int kGroup = FMT == 2 ? 8 : 4;                 // span positions of a load group
+  constexpr int kGroup = kPacked ? 8 : 4;                  // span positions of a load group
   constexpr int kGroups = kDenseLoad * 4 / kGroup;         // load groups per thread and round
-  using Regs = DenseRegs<kGroups, FMT == 2>;
+  using Regs = DenseRegs<kGroups, kPacked>;
   __shared__ __attribute__((aligned(16))) unsigned char smem[O::kBytes];
   const int tid = threadIdx.x;
   auto* lent = reinterpret_cast<u32x4*>(smem + O::kOffEnt);
@@ -1421,13 +1450,17 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     } else {
       lkey[c] = u32x2{0xFFFFFFFFu, 0u};
     }
-    lerr[c] = 0u;
+    if constexpr (!kErrCells) lerr[c] = 0u;
   }
-  if constexpr (FMT == 2) {  // code and flag of every cell: a wave per code, its lanes over the code's cells
+  // FMT 3: the entry of a cell's error spans lies err_off above the cell's own
+  const uint32_t err_off = kErrCells ? 1u << fmt.cell_bits : 0u;
+  if constexpr (kPacked) {  // code and flag of every cell: a wave per code, its lanes over the code's cells
     for (uint32_t c = (uint32_t)tid / kWave; c < ncodes; c += kWavesPerWG) {
       const u32x4 l = lay[c];
-      for (uint32_t k = (uint32_t)tid % kWave; k < l.w; k += kWave)
+      for (uint32_t k = (uint32_t)tid % kWave; k < l.w; k += kWave) {
         lcell[l.z + k] = c << kPackCodeShift | kPackFlag;
+        if constexpr (kErrCells) lcell[err_off + l.z + k] = c << kPackCodeShift | kPackFlag;
+      }
     }
   } else {
     for (uint32_t k = tid; k < ncells; k += kThreads) lcell[k] = 0u;
@@ -1459,7 +1492,7 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     }
   };
   auto escaped = [&](uint32_t w, uint64_t g) {
-    if constexpr (FMT == 2) {
+    if constexpr (kPacked) {
       const uint32_t c = pack_word_escape_code(fmt, w);
       if (c < ncodes) direct(c, pack_word_error(fmt, w), g);
       return;
@@ -1475,6 +1508,23 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
       if ((w >> key_bits) & 1u) atomicAdd(&tab.err[edge], 1ull);
     }
   };
+  // FMT 3, a span that found its entry's flag set: it may be an extreme of its
+  // code c.  Once its cell lies strictly between the code's min and max cells
+  // no later span of the cell is one, with the error bit or without: the flag
+  // goes from both entries of the cell, so an error span — too few per
+  // workgroup and cell to clear a flag of their own — takes the branch no
+  // more often than a plain one.
+  auto extreme = [&](uint32_t w, uint32_t cell, uint32_t c) {
+    const uint32_t key = w & low_mask(key_bits);
+    u32x2 e = lkey[c];
+    if (key < e.x) atomicMin(&lent1[2u * c], key);
+    if (key > e.y) atomicMax(&lent1[2u * c + 1u], key);
+    e = lkey[c];
+    if (cell > (e.x >> fmt.res_bits) && cell < (e.y >> fmt.res_bits)) {
+      atomicAnd(&lcell[cell], ~kPackFlag);
+      atomicAnd(&lcell[err_off + cell], ~kPackFlag);
+    }
+  };
   // w: the span word of position g.  FMT 0: a code past the layout's
   // (kWordNoCode: no span here) is skipped, so no index below leaves the carve;
   // the escape load is taken by the lanes that need it only.  FMT 1: a cell
@@ -1488,7 +1538,19 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
         return;
       }
       if constexpr ((ANOMOD_ABL & 96) == 96) {  // keep the loads, do nothing
-        if (w == (FMT == 2 ? 0x9E3779u : 0x9E3779B9u)) tab.err[0] = w;
+        if (w == (kPacked ? 0x9E3779u : 0x9E3779B9u)) tab.err[0] = w;
+        return;
+      }
+      if constexpr (kErrCells) {
+        // As FMT 2 below, but an error span counts in the error entry of its
+        // cell (w >> res_bits = error << cell_bits | cell): the flush reads the
+        // error count off the entries, and the branch is left to the spans
+        // that may be an extreme.
+        const uint32_t old = atomicAdd(&lcell[pack_word_entry(fmt, w)], 1u), c = old >> kPackCodeShift;
+        if constexpr (!(ANOMOD_ABL & 32)) {
+          atomicAdd(&lsum[c * C::kReps + rep], cell_word_residual(fmt, w));
+          if (__builtin_expect((old & kPackFlag) != 0u, 0)) extreme(w, cell, c);
+        }
         return;
       }
       if constexpr (FMT == 2) {
@@ -1570,7 +1632,7 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
   if (blockIdx.x == 0 && tid < 2 * kGroup) {
     const uint64_t g = tid < kGroup ? lo + (uint64_t)tid : a1 + (uint64_t)(tid - kGroup);
     if (g < (tid < kGroup ? a0 : hi)) {
-      if constexpr (FMT == 2) {
+      if constexpr (kPacked) {
         const uint32_t w = pack_join(reinterpret_cast<const uint16_t*>(word)[g], wlo[g]);
         const uint32_t cell = cell_word_cell(fmt, w);
         if (cell < ncells)
@@ -1584,7 +1646,7 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
   }
   const uint64_t ng = (a1 - a0) / kG;
   // (FMT 2: a0 is a multiple of 8, so both planes' groups are aligned)
-  const u32x4* w4 = FMT == 2 ? reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(word) + a0)
+  const u32x4* w4 = kPacked ? reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(word) + a0)
                              : reinterpret_cast<const u32x4*>(word + a0);
   // groups past the end re-read the last one (no branch around a load) and
   // take skip words
@@ -1595,7 +1657,7 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
       const uint64_t gc = gi < ng ? gi : ng - 1;
       const u32x4 w = w4[gc];
       R.w[j] = gi < ng ? w : u32x4{kWordSkip, kWordSkip, kWordSkip, kWordSkip};
-      if constexpr (FMT == 2) {
+      if constexpr (kPacked) {
         const u32x2 b = reinterpret_cast<const u32x2*>(wlo + a0)[gc];
         R.b[j] = gi < ng ? b : u32x2{kWordSkip, kWordSkip};
       }
@@ -1612,7 +1674,7 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
 #pragma unroll
     for (int j = 0; j < kGroups; ++j) {
       const uint64_t g = a0 + kG * (g0 + (uint64_t)(j * kThreads + tid));
-      if constexpr (FMT == 2) {
+      if constexpr (kPacked) {
         const u32x4 h = cur.w[j];
         const u32x2 b = cur.b[j];
         // span j of the group: half j & 1 of h[j / 2] above byte j & 3 of b[j / 4]
@@ -1643,8 +1705,14 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     const u32x4 l = lay[c];
     unsigned long long* h = tab.hist + (uint64_t)l.x * kBins + l.y;
     unsigned long long part = 0ull;
+    uint32_t nerr = 0u;  // FMT 3: the code's error spans, off its cells' error entries
     for (uint32_t k = lane; k < l.w; k += kWave) {
-      const uint32_t cnt = FMT == 2 ? lcell[l.z + k] & kPackCount : lcell[l.z + k];
+      uint32_t cnt = kPacked ? lcell[l.z + k] & kPackCount : lcell[l.z + k];
+      if constexpr (kErrCells) {
+        const uint32_t n1 = lcell[err_off + l.z + k] & kPackCount;
+        cnt += n1;
+        nerr += n1;
+      }
       if (cnt) {
         atomicAdd(&h[k], (unsigned long long)cnt);
         if constexpr (FMT >= 1) part += (unsigned long long)cnt * hist_lo(l.y + k);
@@ -1653,6 +1721,10 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
     if constexpr (FMT >= 1 && !(ANOMOD_ABL & 32)) {
       for (int o = kWave / 2; o > 0; o >>= 1) part += __shfl_xor(part, o);
       if (lane == 0 && part) atomicAdd(&tab.sum[l.x], part);
+      if constexpr (kErrCells) {
+        for (int o = kWave / 2; o > 0; o >>= 1) nerr += __shfl_xor(nerr, o);
+        if (lane == 0 && nerr) atomicAdd(&tab.err[l.x], (unsigned long long)nerr);
+      }
     }
   }
   for (uint32_t c = tid; c < ncodes; c += kThreads) {
@@ -1663,7 +1735,8 @@ __global__ __launch_bounds__(kThreads, TIER == 0 ? 8 : 4) void edge_dense_kernel
         unsigned long long sum = 0ull;
         for (uint32_t k = 0; k < C::kReps; ++k) sum += lsum[c * C::kReps + k];
         atomicAdd(&tab.sum[l.x], sum);
-        if (lerr[c]) atomicAdd(&tab.err[l.x], (unsigned long long)lerr[c]);
+        if constexpr (!kErrCells)
+          if (lerr[c]) atomicAdd(&tab.err[l.x], (unsigned long long)lerr[c]);
         atomicMin(&tab.mn[l.x], cell_key_dur(fmt, e.x, l.y, l.z));
         atomicMax(&tab.mx[l.x], cell_key_dur(fmt, e.y, l.y, l.z));
       }
@@ -2136,6 +2209,12 @@ bool pack_allowed() {
   const char* f = getenv("ANOMOD_DENSE_PACK");
   return !(f && !strcmp(f, "0"));
 }
+// ANOMOD_DENSE_ERRCELLS=0: a packed layout of the small carve keeps
+// edge_dense_kernel<0, 2>, its error count in the span path (A/B).
+bool errcells_allowed() {
+  const char* f = getenv("ANOMOD_DENSE_ERRCELLS");
+  return !(f && !strcmp(f, "0"));
+}
 
 // The set's layout for S from one of its own tables (count / min / max per
 // edge, on the host): codes by edge order, bin ranges back to back in the
@@ -2153,7 +2232,7 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
   d.codes = d.cells = 0;
   d.streams = 0;
   d.wgs_per_cu = 0;
-  d.cell_words = d.pack = false;
+  d.cell_words = d.pack = d.errcells = false;
   d.host.clear();
   const char* sh = getenv("ANOMOD_DENSE_SHRINK");
   const bool shrink = sh && !strcmp(sh, "1");
@@ -2197,6 +2276,10 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
     // ... and packed, 3 B per span, when the layout also keeps to 256 codes and
     // 15 cell bits (span_word.h)
     d.pack = d.cell_words && pack_allowed() && pack_fmt_fits(d.fmt, d.codes);
+    // ... read by the kernel with error cells when the small carve has room for
+    // two entries per cell, the error entry 2^cell_bits above the cell's own
+    d.errcells = d.pack && d.tier == 0 && errcells_allowed() &&
+                 (1ull << d.fmt.cell_bits) + d.cells <= DenseCfg<2>::kCells;
   } else {
     d.host.clear();
   }
@@ -2213,6 +2296,9 @@ void dense_learn(const anomod_spans* s, uint32_t S, uint32_t E, const unsigned l
     if (d.pack)
       fprintf(stderr, "anomod: edge dense pack S=%u bytes=3 cell_bits=%u res_bits=%u\n", S,
               pack_fmt(d.fmt).cell_bits, pack_fmt(d.fmt).res_bits);
+    if (d.errcells)
+      fprintf(stderr, "anomod: edge dense errcells S=%u entries=%u\n", S,
+              (1u << d.fmt.cell_bits) + d.cells);
   }
 }
 
@@ -2294,9 +2380,10 @@ int dense_encode(anomod_ctx* ctx, const anomod_spans* s, uint32_t S, uint32_t* h
 // replicas without a carry).  ANOMOD_DENSE_WGS caps the grid (tests, A/B).
 int launch_dense(anomod_ctx* ctx, const anomod_spans* s, const Table& tab) {
   DenseSet& d = *s->dense;
-  const int f = d.pack ? 2 : d.cell_words ? 1 : 0;
+  const int f = d.pack ? (d.errcells ? 3 : 2) : d.cell_words ? 1 : 0;
   auto fn = d.tier ? (f == 2 ? edge_dense_kernel<1, 2> : f ? edge_dense_kernel<1, 1> : edge_dense_kernel<1, 0>)
-                   : (f == 2 ? edge_dense_kernel<0, 2> : f ? edge_dense_kernel<0, 1> : edge_dense_kernel<0, 0>);
+            : f == 3 ? edge_dense_kernel<0, 3>
+                     : (f == 2 ? edge_dense_kernel<0, 2> : f ? edge_dense_kernel<0, 1> : edge_dense_kernel<0, 0>);
   if (d.wgs_per_cu <= 0) {  // resident workgroups per CU, asked once per layout
     int per_cu = 0;
     ANOMOD_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(

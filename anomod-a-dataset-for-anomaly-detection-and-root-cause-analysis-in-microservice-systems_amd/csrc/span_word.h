@@ -183,6 +183,11 @@ ANOMOD_HD inline uint32_t pack_word_encode(CellFmt p, uint32_t code, bool error,
 // the code an escape word carries
 ANOMOD_HD inline uint32_t pack_word_escape_code(CellFmt p, uint32_t w) { return w & low_mask(p.res_bits); }
 ANOMOD_HD inline bool pack_word_error(CellFmt p, uint32_t w) { return ((w >> cell_key_bits(p)) & 1u) != 0u; }
+// The entry of a word with a cell of the layout in a cell array that keeps the
+// error spans of a cell apart, 2^cell_bits entries above the cell's own:
+// error << cell_bits | cell, one shift (nothing above the error bit in a
+// packed word).  Below 2^cell_bits + cells.
+ANOMOD_HD inline uint32_t pack_word_entry(CellFmt p, uint32_t w) { return w >> p.res_bits; }
 ANOMOD_HD inline uint16_t pack_hi(uint32_t w) { return (uint16_t)(w >> 8); }
 ANOMOD_HD inline uint8_t pack_lo(uint32_t w) { return (uint8_t)(w & 0xFFu); }
 ANOMOD_HD inline uint32_t pack_join(uint32_t hi16, uint32_t lo8) { return hi16 << 8 | lo8; }
