@@ -23,7 +23,7 @@ from .engine import (Experiment, Features, SymptomCorrelation, default_context, 
 from . import api
 from .segments import SegmentSet, service_name_of, trace_infos
 from .writers import jaeger_to_csv, write_jaeger_csv, write_metric_long_csv
-from .spans import (CallRepeats, CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
+from .spans import (CallRepeats, CallTransit, CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
                     TraceShapes, TraceSpectrum, TraceStructure, edge_rows, spectrum_thresholds)
 
 __all__ = [
@@ -39,7 +39,7 @@ __all__ = [
     "jaeger_to_csv", "write_jaeger_csv", "write_metric_long_csv", "decode_native",
     "load_trace_file", "api", "trace_window_scores", "TraceSpectrum", "spectrum_thresholds",
     "CriticalPath", "TraceShapes", "ErrorOrigins", "EdgeLoad", "EdgeExemplars", "load_window_scores",
-    "SymptomCorrelation", "walk_graph", "CallRepeats",
+    "SymptomCorrelation", "walk_graph", "CallRepeats", "CallTransit",
 ]
 
 

@@ -1,6 +1,6 @@
 """CLI:  python -m anomod features <trace file|dir> [--metrics PATH] [--out FILE]
                                  [--spectrum] [--critical-path] [--shapes]
-                                 [--error-origins] [--repeats]
+                                 [--error-origins] [--repeats] [--transit]
                                  [--trace-step S [--trace-load]]
                                  [--exemplars K]
                                  [--trace-step S --symptom-corr [--walk correlation]]
@@ -73,6 +73,34 @@ def call_repeats_doc(rep) -> dict:
             "max_size": int(rep.max_size),
             "services": {s: {k: int(v[i]) for k, v in cols.items()}
                          for i, s in enumerate(rep.services)}}
+
+
+def call_transit_doc(tr) -> dict:
+    """The "call_transit" object of the features JSON: the calls, the paired
+    ones among them and, per callee service over the cross-service incoming
+    rows, the paired calls, the request / response records with their mean
+    gap in microseconds (None without a record) and the largest row p99 of
+    each table (None without one), and the early (clock skew), late
+    (abandoned) and untimed calls."""
+    S = len(tr.services)
+    cols = {k: tr.per_service(k) for k in ("paired", "early", "late", "untimed")}
+
+    def table(t, name):
+        cnt, tot = tr.per_service(name + ".count"), tr.per_service(name + ".sum_us")
+        p99 = np.where(t.count[:S * S] > 0, np.nan_to_num(t.p99_us[:S * S], nan=-1.0), -1.0)
+        p99 = p99.reshape(S, S).copy()
+        np.fill_diagonal(p99, -1.0)
+        top = p99.max(axis=0)
+        return [{"records": int(cnt[i]),
+                 "mean_us": float(tot[i]) / float(cnt[i]) if cnt[i] else None,
+                 "p99_us": float(top[i]) if top[i] >= 0 else None} for i in range(S)]
+
+    req, resp = table(tr.request, "request"), table(tr.response, "response")
+    return {"calls": int(tr.calls), "paired": int(tr.paired),
+            "services": {s: {"paired": int(cols["paired"][i]), "request": req[i],
+                             "response": resp[i], "early": int(cols["early"][i]),
+                             "late": int(cols["late"][i]), "untimed": int(cols["untimed"][i])}
+                         for i, s in enumerate(tr.services)}}
 
 
 def edge_load_doc(load) -> dict:
@@ -198,6 +226,12 @@ def main(argv=None) -> int:
                         "callee more than once (retries, retry storms, N+1 loops), score the "
                         "growth of that amplification against --baseline, and write the "
                         "counts as \"call_repeats\"")
+    f.add_argument("--transit", action="store_true",
+                   help="also measure, per edge, the time between two services (the request "
+                        "gap from a client span's start to the callee's start and the response "
+                        "gap back; needs span start times), count the calls the caller "
+                        "abandoned and those that show clock skew, score the growth of the "
+                        "gaps against --baseline, and write it as \"call_transit\"")
     f.add_argument("--exemplars", type=int, metavar="K",
                    help="also list, for each of the top 5 ranked services, the K slowest calls "
                         "of its slowest incoming edge and the K slowest failed calls of its "
@@ -234,13 +268,14 @@ def main(argv=None) -> int:
     if args.baseline:
         baseline = features(load_experiment(args.baseline), W=args.window,
                             self_time=args.self_time, critical_path=args.critical_path,
-                            shapes=args.shapes, repeats=args.repeats)
+                            shapes=args.shapes, repeats=args.repeats, transit=args.transit)
     feats = features(exp, W=args.window, trace_step_s=args.trace_step,
                      self_time=args.self_time, baseline=baseline, spectrum=args.spectrum,
                      critical_path=args.critical_path, trace_quantile=args.trace_quantile,
                      shapes=args.shapes, error_origins=args.error_origins,
                      trace_load=args.trace_load, exemplars=args.exemplars,
-                     symptom_corr=args.symptom_corr, repeats=args.repeats)
+                     symptom_corr=args.symptom_corr, repeats=args.repeats,
+                     transit=args.transit)
     ranking = rank(feats, walk=args.walk, alpha=args.alpha)
     doc = {
         "experiment": exp.name,
@@ -279,6 +314,8 @@ def main(argv=None) -> int:
         doc["loop_spans"] = int(feats.error_origins.loop_spans)
     if feats.repeats is not None:
         doc["call_repeats"] = call_repeats_doc(feats.repeats)
+    if feats.transit is not None:
+        doc["call_transit"] = call_transit_doc(feats.transit)
     if feats.edge_load is not None:
         doc["edge_load"] = edge_load_doc(feats.edge_load)
         doc["load_scores"] = dict(zip(feats.edges.services,

@@ -40,6 +40,8 @@ HOST_SLOTS = 5
 HOST_SLOT_NAMES = ("group_alloc", "group_pinned", "group_wall", "upload_setup", "set_alloc")
 NO_PARENT = 0xFFFFFFFF
 SPAN_ROOT, SPAN_FIRST = 0x1, 0x2
+# anomod_call_transit.span_state bits
+TRANSIT_CALL, TRANSIT_PAIRED, TRANSIT_TIMED, TRANSIT_EARLY, TRANSIT_LATE = 1, 2, 4, 8, 16
 
 
 class AnomodError(RuntimeError):
@@ -199,6 +201,24 @@ class CallRepeatsC(C.Structure):
     ]
 
 
+class CallTransitC(C.Structure):
+    _fields_ = [
+        ("n_services", C.c_uint32),
+        ("calls", C.c_uint64),
+        ("paired", C.c_uint64),
+        ("request", C.POINTER(EdgeTableC)),
+        ("response", C.POINTER(EdgeTableC)),
+        ("untimed", C.POINTER(C.c_uint64)),
+        ("early", C.POINTER(C.c_uint64)),
+        ("late", C.POINTER(C.c_uint64)),
+        ("early_us", C.POINTER(C.c_uint64)),
+        ("late_us", C.POINTER(C.c_uint64)),
+        ("span_req_us", C.POINTER(C.c_uint32)),
+        ("span_resp_us", C.POINTER(C.c_uint32)),
+        ("span_state", C.POINTER(C.c_uint8)),
+    ]
+
+
 class TraceStructC(C.Structure):
     _fields_ = [
         ("n_services", C.c_uint32),
@@ -323,6 +343,7 @@ _SIGS = {
     "anomod_trace_shapes_spans": (_i32, [_vp, _vp, _P(TraceShapesC)]),
     "anomod_error_origins_spans": (_i32, [_vp, _vp, _P(ErrorOriginsC)]),
     "anomod_call_repeats_spans": (_i32, [_vp, _vp, _P(CallRepeatsC)]),
+    "anomod_call_transit_spans": (_i32, [_vp, _vp, _P(CallTransitC)]),
     "anomod_edge_aggregate_host": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _u32, _i32,
                                           _P(_i32), _P(_i32), _P(EdgeTableC)]),
     "anomod_edge_aggregate": (_i32, [_vp, _P(SpanSoA), _u64, _P(_u64), _u64, _P(EdgeTableC)]),

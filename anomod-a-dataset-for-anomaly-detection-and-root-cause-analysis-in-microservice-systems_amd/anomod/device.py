@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from .spans import (CallRepeats, CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
+from .spans import (CallRepeats, CallTransit, CriticalPath, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
                     TraceShapes, TraceSpectrum, TraceStructure, edge_rows)
 
 
@@ -739,6 +739,45 @@ class Context:
             cr.grouped_spans, cr.max_size = int(cs.grouped_spans), int(cs.max_size)
             cr.timed = bool(cs.timed)
             return cr
+        finally:
+            if tmp is not None:
+                tmp.free()
+
+    def call_transit(self, spans: DeviceSpans | SpanSet, with_hist: bool = True,
+                     per_span: bool = False) -> CallTransit:
+        """Call transit of a grouped set with start times
+        (anomod_call_transit_spans): for every call whose parent span made no
+        other call, the request gap (parent's start to the call's start) and
+        the response gap (the call's end to the parent's end) as two edge
+        tables, and per edge row the calls that start before their parent
+        (early: clock skew), end after it (late: abandoned by the caller) or
+        have no start time (untimed).  per_span=True also returns
+        span_req_us, span_resp_us and span_state (TRANSIT_* bits) by span
+        position.  With a communicator attached the two tables are merged over
+        the ranks; everything else is rank-local.  A host set is uploaded for
+        the call."""
+        tmp = None
+        if isinstance(spans, SpanSet):
+            if spans.start_us is None:
+                raise ValueError("span set has no start_us column")
+            tmp = spans = self.upload(spans)
+        try:
+            S = len(spans.services)
+            tr = CallTransit.empty(spans.services, with_hist,
+                                   int(spans.n_spans) if per_span else None)
+            req, resp = tr.request.c_struct(), tr.response.c_struct()
+            cs = L.CallTransitC(S, 0, 0, C.pointer(req), C.pointer(resp),
+                                *(L.ptr(getattr(tr, k), C.c_uint64) for k in tr.TABLES),
+                                L.ptr(tr.span_req_us, C.c_uint32),
+                                L.ptr(tr.span_resp_us, C.c_uint32),
+                                L.ptr(tr.span_state, C.c_uint8))
+            self._check(self._lib.anomod_call_transit_spans(self.handle, spans.handle,
+                                                            C.byref(cs)))
+            tr.calls, tr.paired = int(cs.calls), int(cs.paired)
+            for t in (tr.request, tr.response):
+                if t.hist is not None:
+                    t.hist = t.hist.reshape(edge_rows(S), L.HIST_BINS)
+            return tr
         finally:
             if tmp is not None:
                 tmp.free()

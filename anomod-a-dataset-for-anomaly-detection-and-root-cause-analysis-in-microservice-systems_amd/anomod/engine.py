@@ -26,7 +26,7 @@ import numpy as np
 
 from . import decode
 from .device import Context, SynthSpec, synth_generate_host
-from .spans import (CallRepeats, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
+from .spans import (CallRepeats, CallTransit, EdgeExemplars, EdgeLoad, EdgeTable, EdgeWindows, ErrorOrigins, SpanSet,
                     TraceShapes, TraceSpectrum, edge_rows, spectrum_thresholds)
 
 # --------------------------------------------------------------------------
@@ -216,6 +216,8 @@ class Features:
     error_origins: ErrorOrigins | None = None
     # features(repeats=True): repeated and retried calls per edge
     repeats: CallRepeats | None = None
+    # features(transit=True): request and response gaps per edge
+    transit: CallTransit | None = None
     # features(trace_load=True): per-window busy time and carried calls of every edge
     edge_load: EdgeLoad | None = None
     # features(exemplars=K): the K slowest calls of every edge, and the K
@@ -316,6 +318,34 @@ def _repeat_shift(cur: CallRepeats, base: CallRepeats, min_groups: int = 10) -> 
     shift = np.zeros(cur.groups.shape[0])
     shift[ok] = np.maximum(0.0, np.log2(cur.amplification()[ok] / ba[ok]))
     return shift.reshape(S + 2, S).max(axis=0)
+
+
+def _transit_shift(cur: CallTransit, base: CallTransit, min_count: int = 10) -> np.ndarray:
+    """Per service: largest log2 growth of the p99 of an incoming
+    cross-service row (p < S, p != c: a handler's gap to its own client span
+    is work, not transit) of the request or the response table over the same
+    row — matched by service NAMES, as _latency_shift matches them — in a
+    baseline run (>= min_count records on both sides in the table in question,
+    a finite baseline p99 > 0); never below 0."""
+    S, Sb = len(cur.services), len(base.services)
+    pos = {s: i for i, s in enumerate(base.services)}
+    m = np.array([pos.get(s, -1) for s in cur.services], np.int64)
+    p_cur = np.repeat(np.arange(S), S)
+    c_cur = np.tile(np.arange(S), S)
+    pb, cb = m[p_cur], m[c_cur]
+    have = (pb >= 0) & (cb >= 0) & (p_cur != c_cur)
+    rows = np.where(have, pb * Sb + np.where(cb >= 0, cb, 0), 0)
+    out = np.zeros(S)
+    for tc, tb in ((cur.request, base.request), (cur.response, base.response)):
+        cc, cp = tc.count[:S * S], tc.p99_us[:S * S]
+        bc = np.where(have, tb.count[rows], 0)
+        bp = np.where(have, tb.p99_us[rows], np.nan)
+        ok = (have & (cc >= min_count) & (bc >= min_count) & np.isfinite(cp) & np.isfinite(bp)
+              & (bp > 0))
+        shift = np.zeros(S * S)
+        shift[ok] = np.maximum(0.0, np.log2(cp[ok] / bp[ok]))
+        out = np.maximum(out, shift.reshape(S, S).max(axis=0))
+    return out
 
 
 def _squash(x: np.ndarray) -> np.ndarray:
@@ -499,7 +529,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
              trace_quantile: int | None = None, shapes: bool = False,
              error_origins: bool = False, trace_load: bool = False,
              exemplars: int | None = None, symptom_corr: bool = False,
-             corr_min_pairs: int = 3, repeats: bool = False) -> Features:
+             corr_min_pairs: int = 3, repeats: bool = False,
+             transit: bool = False) -> Features:
     """GPU features of one experiment (SURVEY.md §3 stack D steps 4-7).  With
     trace_step_s (seconds; the span set needs start_us) the spans also go
     through the per-window edge table -> EWMA/z -> trace_window_scores, and
@@ -568,6 +599,19 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     components["repeat_shift"]: the largest log2 growth of an incoming row's
     amplification over the same row of the baseline (rows matched by service
     names, >= 10 groups on both sides); without a baseline no score changes.
+    With transit (the span set needs start_us) the result also holds the call
+    transit (Context.call_transit: for every call whose parent span made no
+    other call, the request gap from the caller's client span to the callee
+    and the response gap back) with components["abandoned_rate"] — per callee
+    service over the cross-service incoming rows, the share of the timed
+    calls whose caller ended first — and components["skew_rate"] — the share
+    that start before their caller.  Against a baseline that has transit the
+    score gains 0.25 * the squashed components["transit_shift"], added after
+    every other term: the largest log2 growth of the request or response p99
+    of a cross-service incoming row over the same row of the baseline (rows
+    matched by service names, >= 10 records on both sides): time lost between
+    two services, which leaves the callee's duration and self time where they
+    were; without a baseline no score changes.
     Non-finite window scores: a column whose score is NaN is skipped, +inf
     squashes to 1, so service_scores stays finite."""
     if trace_load and trace_step_s is None:
@@ -578,6 +622,8 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
         raise ValueError("features(symptom_corr=True) needs trace_step_s")
     if trace_quantile is not None and not 0 <= int(trace_quantile) <= 99:
         raise ValueError(f"features(trace_quantile={trace_quantile}): a percentage in [0, 99]")
+    if transit and getattr(exp.spans, "start_us", None) is None:
+        raise ValueError("features(transit=True) needs a span set with start_us")
     ctx = ctx or default_context()
     edges = ctx.edge_aggregate(exp.spans, with_hist=with_hist)
     self_edges = ctx.self_time(exp.spans, with_hist=with_hist) if self_time else None
@@ -653,6 +699,15 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
             shift = _repeat_shift(rep_table, baseline.repeats)
             params["components"]["repeat_shift"] = shift
             rep_term = 0.25 * _squash(shift)   # added last: the other terms sum as without it
+    tr_table, tr_term = None, None
+    if transit:
+        tr_table = ctx.call_transit(exp.spans, with_hist=with_hist)
+        params["components"]["abandoned_rate"] = tr_table.abandoned_rate()
+        params["components"]["skew_rate"] = tr_table.skew_rate()
+        if baseline is not None and baseline.transit is not None:
+            shift = _transit_shift(tr_table, baseline.transit)
+            params["components"]["transit_shift"] = shift
+            tr_term = 0.25 * _squash(shift)   # added after every other term, the repeat term included
     ex = err_ex = None
     if exemplars is not None:
         ex = ctx.edge_exemplars(exp.spans, int(exemplars))
@@ -660,9 +715,12 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
     if trace_step_s is None:
         if rep_term is not None:
             score = score + rep_term
+        if tr_term is not None:
+            score = score + tr_term
         return Features(exp.name, edges, Z, series, score, params, self_edges=self_edges,
                         spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
-                        exemplars=ex, error_exemplars=err_ex, repeats=rep_table)
+                        exemplars=ex, error_exemplars=err_ex, repeats=rep_table,
+                        transit=tr_table)
     win, ts, mm0 = _trace_windows(exp.spans, ctx, trace_step_s, trace_W, trace_eps,
                                   trace_min_count, trace_quantile)
     tsq = _squash(ts)  # the metric term's squashing
@@ -688,10 +746,13 @@ def features(exp: Experiment, ctx: Context | None = None, *, W: int = 60,
             params["components"]["metric_corr"] = sc.metric_service
     if rep_term is not None:
         score = score + rep_term
+    if tr_term is not None:
+        score = score + tr_term
     return Features(exp.name, edges, Z, series, score, params, symptom_corr=sc,
                     edge_windows=win, trace_window_scores=ts, self_edges=self_edges,
                     spectrum=spec, cp_edges=cp_edges, shapes=census, error_origins=origins,
-                    edge_load=load, exemplars=ex, error_exemplars=err_ex, repeats=rep_table)
+                    edge_load=load, exemplars=ex, error_exemplars=err_ex, repeats=rep_table,
+                    transit=tr_table)
 
 
 def walk_graph(edges: EdgeTable, corr: np.ndarray, rho: float = 0.2

@@ -702,6 +702,86 @@ class CallRepeats:
                          where=g > 0)
 
 
+@dataclass
+class CallTransit:
+    """Call transit of a span set (anomod_call_transit_spans): for a call whose
+    parent span made no other call (a client / exit span and the callee's
+    server / entry span), the request gap from the parent's start to the
+    call's start and the response gap from the call's end to the parent's.
+    Rows as in EdgeTable; only the first S * S rows hold calls.  A call that
+    starts before its parent is early (clock skew), one that ends after it is
+    late (abandoned: the caller gave up first); neither leaves a record."""
+
+    services: list[str]
+    request: EdgeTable                # the request gaps of the recorded calls
+    response: EdgeTable               # the response gaps
+    untimed: np.ndarray               # u64 [E] paired calls with a start of 0 on either side
+    early: np.ndarray                 # u64 [E] paired, timed calls that start before their parent
+    late: np.ndarray                  # u64 [E] paired, timed calls that end after their parent
+    early_us: np.ndarray              # u64 [E] by how much, summed (each clamped to 2^32 - 1)
+    late_us: np.ndarray               # u64 [E]
+    calls: int = 0                    # spans that have a parent
+    paired: int = 0                   # ... whose parent made no other call
+    span_req_us: np.ndarray | None = None   # u32 [n_spans] (per_span=True)
+    span_resp_us: np.ndarray | None = None  # u32 [n_spans] (per_span=True)
+    span_state: np.ndarray | None = None    # u8 [n_spans] TRANSIT_* bits (per_span=True)
+
+    TABLES = ("untimed", "early", "late", "early_us", "late_us")
+
+    @staticmethod
+    def empty(services: list[str], with_hist: bool = True,
+              n_spans: int | None = None) -> "CallTransit":
+        """Empty tables over `services`; n_spans: also the per-span columns."""
+        E = edge_rows(len(services))
+        return CallTransit(list(services), EdgeTable.empty(services, with_hist),
+                           EdgeTable.empty(services, with_hist),
+                           *(np.zeros(E, np.uint64) for _ in range(5)), 0, 0,
+                           None if n_spans is None else np.zeros(n_spans, np.uint32),
+                           None if n_spans is None else np.zeros(n_spans, np.uint32),
+                           None if n_spans is None else np.zeros(n_spans, np.uint8))
+
+    def paired_rows(self) -> np.ndarray:
+        """u64 [E]: the paired calls of every row (request.count + early + untimed)."""
+        return self.request.count + self.early + self.untimed
+
+    def per_service(self, name: str) -> np.ndarray:
+        """A u64 [E] array summed over the parent rows of the cross-service
+        rows (p < S, p != c): one value per callee service.  name: one of
+        TABLES, "paired", or a table field as "request.count" /
+        "response.sum_us"."""
+        S = len(self.services)
+        if name == "paired":
+            t = self.paired_rows()
+        elif "." in name:
+            tab, field = name.split(".", 1)
+            if tab not in ("request", "response") or field not in ("count", "errors", "sum_us"):
+                raise ValueError(f"per_service({name!r}): no such summable table")
+            t = getattr(getattr(self, tab), field)
+        elif name in self.TABLES:
+            t = getattr(self, name)
+        else:
+            raise ValueError(f"per_service({name!r}): no such summable table")
+        t = t[:S * S].reshape(S, S).copy()
+        np.fill_diagonal(t, 0)
+        return t.sum(axis=0)
+
+    def skew_rate(self) -> np.ndarray:
+        """Per callee service over the cross-service rows: early / (request
+        records + early), the share of the timed calls into it that start
+        before their caller; 0 where there is none."""
+        e = self.per_service("early").astype(np.float64)
+        d = e + self.per_service("request.count").astype(np.float64)
+        return np.divide(e, d, out=np.zeros(len(self.services)), where=d > 0)
+
+    def abandoned_rate(self) -> np.ndarray:
+        """Per callee service over the cross-service rows: late / (response
+        records + late), the share of the timed calls into it whose caller
+        ended first; 0 where there is none."""
+        l = self.per_service("late").astype(np.float64)
+        d = l + self.per_service("response.count").astype(np.float64)
+        return np.divide(l, d, out=np.zeros(len(self.services)), where=d > 0)
+
+
 def spectrum_thresholds(base: EdgeTable, services: list[str], *, rows: str = "root",
                         min_count: int = 10) -> np.ndarray:
     """Latency thresholds (u32 [E] over `services`) for Context.trace_spectrum

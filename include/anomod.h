@@ -812,6 +812,90 @@ typedef struct {
 } anomod_call_repeats;
 int anomod_call_repeats_spans(anomod_ctx* ctx, const anomod_spans* spans,
                               anomod_call_repeats* out);
+/* Call transit of a grouped set with start times: the time lost between two
+ * services — from the moment the caller's client span opens to the moment the
+ * callee's server span starts, and from the callee's end back to the caller's
+ * end.  Retransmits, waiting for a connection, name resolution and a caller
+ * that gives up early all live there; the callee's duration and self time do
+ * not move.
+ *   Spans.   s(i) = start_us[i], e(i) = s(i) + dur_us[i] (u64, saturating at
+ *            2^64 - 1, as the critical-path call).
+ *   Parent.  par(i) is the parent rule of the self-time call: the first span
+ *            of i's trace, in position order, whose id equals i's parent
+ *            reference; none for reference 0, for a reference that names no
+ *            span of the trace, and when the first match is i itself;
+ *            duplicated ids resolve to the first carrier.
+ *   Call.    A span with a parent is a call.  kids(j) is the number of calls
+ *            whose parent is j.
+ *   Paired.  A call c with p = par(c) is paired iff kids(p) == 1: the parent
+ *            span exists only to make this call (a client / exit span).
+ *            Unpaired calls are counted in `calls` only: their gaps would
+ *            include the parent's other work and are not transit.
+ *   Row.     The row of a call is r = svc[p] * S + svc[c], one of the first
+ *            S * S rows of anomod_edge_aggregate_spans.  The ROOT and ORPHAN
+ *            rows stay empty in every output.
+ *   Untimed. A paired call is untimed when start_us[c] == 0 || start_us[p] ==
+ *            0.  It adds untimed[r] += 1 and nothing else.
+ *   A paired, timed call:
+ *            s(c) >= s(p): one record in the request table with value
+ *            min(s(c) - s(p), 2^32 - 1).  Otherwise the call is early:
+ *            early[r] += 1, early_us[r] += min(s(p) - s(c), 2^32 - 1), no
+ *            request record (the callee's clock runs behind the caller's: per
+ *            edge, how far the timing columns can be trusted).
+ *            e(c) <= e(p): one record in the response table with value
+ *            min(e(p) - e(c), 2^32 - 1).  Otherwise the call is late
+ *            (abandoned: the caller gave up while the callee still worked):
+ *            late[r] += 1, late_us[r] += min(e(c) - e(p), 2^32 - 1), no
+ *            response record.
+ *            The two tests are independent: equal starts give a request of 0,
+ *            equal ends a response of 0.
+ *   Tables.  request and response are anomod_edge_tables with the layout,
+ *            histogram bins, p50 / p99 and finalize of every other edge table.
+ *            count / errors are taken over the recorded calls, with the error
+ *            bit being the call's own ANOMOD_FLAG_ERROR; sum / min / max /
+ *            hist over the recorded values.
+ *   Counts.  untimed, early, late, early_us, late_us are u64 [E].
+ *   Scalars. calls is the spans with a parent, paired those that are paired.
+ *   Optional per-span columns, by span position: span_req_us u32 and
+ *            span_resp_us u32, both 0 where nothing was recorded; span_state
+ *            u8 = ANOMOD_TRANSIT_CALL | _PAIRED | _TIMED | _EARLY | _LATE;
+ *            spans outside every trace read 0.
+ * Per row: request.count + early + untimed = the paired calls of the row;
+ * response.count + late = request.count + early; calls = the edge table's
+ * count over the first S * S rows minus the self-referencing spans.  Every
+ * result is an integer, bit-exact for any launch geometry.  The two tables
+ * are required, every other pointer may be NULL (that output is skipped);
+ * n == 0 gives empty tables and zeros; an ungrouped set or a set without a
+ * start column is ANOMOD_ESTATE; a service index >= n_services is
+ * ANOMOD_EINVAL; at most 2^32 - 2 spans per call.  With a communicator
+ * attached the two tables are merged over the ranks (they go through the
+ * record aggregation of the other edge tables, whose status agreement every
+ * rank must reach, so every rank makes the call); the count arrays, the
+ * scalars and the per-span columns stay rank-local (a caller sums the ranks'
+ * arrays itself).  The set's histogram-form hint is neither read nor changed;
+ * an unknown order hint is probed as in the self-time call.                 */
+#define ANOMOD_TRANSIT_CALL 1u
+#define ANOMOD_TRANSIT_PAIRED 2u
+#define ANOMOD_TRANSIT_TIMED 4u
+#define ANOMOD_TRANSIT_EARLY 8u
+#define ANOMOD_TRANSIT_LATE 16u
+typedef struct {
+  uint32_t n_services;         /* in : S; E = (S + 2) * S as in anomod_edge_table  */
+  uint64_t calls;              /* out                                              */
+  uint64_t paired;             /* out                                              */
+  anomod_edge_table* request;  /* required                                         */
+  anomod_edge_table* response; /* required                                         */
+  uint64_t* untimed;           /* [E] host; each array may be NULL                 */
+  uint64_t* early;             /* [E]                                              */
+  uint64_t* late;              /* [E]                                              */
+  uint64_t* early_us;          /* [E]                                              */
+  uint64_t* late_us;           /* [E]                                              */
+  uint32_t* span_req_us;       /* [n_spans] host, may be NULL                      */
+  uint32_t* span_resp_us;      /* [n_spans] host, may be NULL                      */
+  uint8_t* span_state;         /* [n_spans] host, may be NULL                      */
+} anomod_call_transit;
+int anomod_call_transit_spans(anomod_ctx* ctx, const anomod_spans* spans,
+                              anomod_call_transit* out);
 /* One-shot host convenience: upload + aggregate + download.               */
 int anomod_edge_aggregate(anomod_ctx* ctx, const anomod_span_soa* soa, uint64_t n_spans,
                           const uint64_t* trace_ptr, uint64_t n_traces, anomod_edge_table* out);
