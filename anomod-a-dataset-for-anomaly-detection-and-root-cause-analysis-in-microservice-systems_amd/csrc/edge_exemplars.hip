@@ -327,6 +327,9 @@ int anomod_edge_exemplars_spans(anomod_ctx* ctx, const anomod_spans* spans,
   if (log_kernel())  // (tests, timing)
     fprintf(stderr, "anomod: edge exemplars kernel edge_exemplars_kernel<%s>, lists %s\n",
             src.rows ? "rows" : "keys", a.place == kListsLds ? "lds" : "global");
+  stream_log("edge_exemplars_kernel", src.rows ? "rows" : "keys", -1,
+             a.place == kListsLds ? "lds" : a.place == kListsGlobalCached ? "cached" : "global",
+             grid, a.per_wg);
   if (int rc = stage_begin(ctx, kStageEdgeExemplars)) return rc;
   ANOMOD_HIP(ctx, hipMemsetAsync(a.misc, 0, b_zero, ctx->stream));
   if (int rc = src.fill(ctx, spans, S, w)) return rc;

@@ -353,6 +353,7 @@ int anomod_edge_load_spans(anomod_ctx* ctx, const anomod_spans* spans, anomod_ed
   if (log_kernel())  // (tests, timing)
     fprintf(stderr, "anomod: edge load kernel edge_load_kernel<%s>, tile %u windows\n",
             src.rows ? "rows" : "keys", a.Wt);
+  stream_log("edge_load_kernel", src.rows ? "rows" : "keys", a.Wt, nullptr, grid, a.per_wg);
   if (int rc = stage_begin(ctx, kStageEdgeLoad)) return rc;
   ANOMOD_HIP(ctx, hipMemsetAsync(a.misc, 0, b_tab, ctx->stream));
   if (int rc = src.fill(ctx, spans, S, w)) return rc;

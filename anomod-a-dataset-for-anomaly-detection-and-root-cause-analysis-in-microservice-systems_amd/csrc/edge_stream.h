@@ -304,6 +304,12 @@ int stream_geometry(anomod_ctx* ctx, Fn fn, int threads, size_t lds, uint64_t n,
   return ANOMOD_OK;
 }
 
+// Under log_kernel() (tests): the geometry of one stream launch on stderr,
+//   anomod: stream KERNEL<FORM>[, tile N windows][, lists PLACE], grid G, P spans per workgroup
+// tile < 0: a kernel without a window ring; lists NULL: one without lists.
+void stream_log(const char* kernel, const char* form, int64_t tile, const char* lists,
+                uint64_t grid, uint64_t per_wg);
+
 // A result table queued back to the host when the caller asked for it (dst != NULL).
 hipError_t stream_back(anomod_ctx* ctx, void* dst, const void* src, size_t bytes);
 // The end of a call: the two counter words back (after the tables the caller

@@ -69,6 +69,16 @@ uint64_t stream_grid(const anomod_ctx* ctx, uint64_t n, uint64_t batch, int per_
   return (n + *per_wg - 1) / *per_wg;
 }
 
+void stream_log(const char* kernel, const char* form, int64_t tile, const char* lists,
+                uint64_t grid, uint64_t per_wg) {
+  if (!log_kernel()) return;
+  char ring[40] = "", place[40] = "";
+  if (tile >= 0) snprintf(ring, sizeof ring, ", tile %lld windows", (long long)tile);
+  if (lists) snprintf(place, sizeof place, ", lists %s", lists);
+  fprintf(stderr, "anomod: stream %s<%s>%s%s, grid %llu, %llu spans per workgroup\n", kernel, form,
+          ring, place, (unsigned long long)grid, (unsigned long long)per_wg);
+}
+
 hipError_t stream_back(anomod_ctx* ctx, void* dst, const void* src, size_t bytes) {
   return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
 }

@@ -231,6 +231,7 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   a.TE = TE;
   a.misc = misc_d;
   uint64_t grid = cell_grid(ctx, n, &a.per_wg);
+  stream_log("window_cell_keys_kernel", "keys", -1, nullptr, grid, a.per_wg);
   hipLaunchKernelGGL(window_cell_keys_kernel, dim3((unsigned)grid), dim3(kCellThreads), 0,
                      ctx->stream, a);
   ANOMOD_HIP(ctx, hipGetLastError());
@@ -250,6 +251,7 @@ int anomod_edge_window_quantiles_spans(anomod_ctx* ctx, const anomod_spans* span
   ba.cbegin = cbegin;
   ba.cend = cend;
   grid = cell_grid(ctx, m, &ba.per_wg);
+  stream_log("window_cell_bounds_kernel", "keys", -1, nullptr, grid, ba.per_wg);
   hipLaunchKernelGGL(window_cell_bounds_kernel, dim3((unsigned)grid), dim3(kCellThreads), 0,
                      ctx->stream, ba);
   ANOMOD_HIP(ctx, hipGetLastError());

@@ -294,6 +294,7 @@ int anomod_edge_windows_spans(anomod_ctx* ctx, const anomod_spans* spans,
   if (int rc = stream_geometry(ctx, edge_windows_kernel, kWinThreads, lds, n,
                                "ANOMOD_EDGE_WINDOWS_WGS", &a.per_wg, &grid))
     return rc;
+  stream_log("edge_windows_kernel", "keys", a.Wt, nullptr, grid, a.per_wg);
   if (int rc = stage_begin(ctx, kStageEdgeWindows)) return rc;
   ANOMOD_HIP(ctx, hipMemsetAsync(a.misc, 0, b_tab, ctx->stream));
   if (int rc = span_edge_keys(ctx, spans, S, keys, ws)) return rc;
